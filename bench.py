@@ -15,7 +15,10 @@ Workloads (BASELINE.json configs; the default is c5, the north-star configuratio
       scaling), 10^7-entry table replicated.
   c3  6-frame pass (KmerReference.java:157-203) over a rank's 5 Mbp synthetic genome.
 
-Beside the timed steps, rank 0 of a 1-GPU run also reports
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints
+the result line with the headline figure (value, ms_per_step) and nothing that takes a run of
+its own. With --full, beside the timed steps, every rank repeats the K steps with the library's
+hipEvents around its kernels (phases_ms) and rank 0 of a 1-GPU run also reports
   roofline      the dominant kernel's SURVEY §8(d) algorithmic bytes per launch (64 B per
                 probed window + its input) over its hipEvent-timed duration against 8 TB/s
                 (`achieved`, `frac`); beside it the HBM bytes it really moves (`traffic`,
@@ -29,10 +32,22 @@ Beside the timed steps, rank 0 of a 1-GPU run also reports
                 host cores (and on one core), on a bounded sample of the same batch and the
                 same full table.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c2|c3|c4]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c2|c3|c4] [--full]
+                   [--dump-outputs DIR]
   python bench.py --workload genomes|fasta   (the drop-in's command-level regimes: `kma apply`
                   over a GTO directory / `kma apply-fasta` over a protein FASTA file)
   torchrun --nproc-per-node N bench.py --gpus N ...
+
+--dump-outputs DIR writes what the timed path computed, as a caller of it receives it after the
+last timed step, into DIR/<name>.npy (float64; rank 0's arrays, rank r > 0's as <name>.rank<r>):
+fid, count, status per protein and the job's per-function tally (c5 / c2 / c4), or the hit
+records' columns and their number (c3). The inputs are seeded, so two builds run with the same
+arguments can be compared array for array. Outputs above 64 MB in all are cut to a fixed seeded
+sample of their rows.
+
+The c5 inputs come from the copy the build keeps (kmeranno.synth_cache: the same arrays the
+generator makes, read in a second instead of generated in most of a minute), any other size
+from the generator.
 
 Prints ONE JSON line on rank 0.
 """
@@ -56,6 +71,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "kmers.anno_amd", "python")]
 import kmeranno  # noqa: E402
 from kmeranno import dist as kdist  # noqa: E402
 from kmeranno import synth  # noqa: E402
+from kmeranno import synth_cache  # noqa: E402
 
 K = 8
 MIN_HITS = 5
@@ -66,6 +82,7 @@ GATHER_BIN = os.path.join(ROOT, "kmers.anno_amd", "build", "kma_gather_bench")
 # Per-launch PMC traffic of the dominant kernels of this build (scripts/gpu_traffic.sh +
 # scripts/traffic_summary.py).
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "r06_traffic.json")
+DUMP_BUDGET = 64_000_000  # --dump-outputs: bytes written at most, over all files
 METRIC = "kmer lookups/s + seqs annotated/s at 1/2/4/8 GPUs; achieved HBM GB/s vs roofline"
 WORKLOADS = {
     "c2": "10k synthetic proteins (small.gto CDS length distribution) vs 10M-entry protein "
@@ -91,6 +108,21 @@ def host_threads() -> int:
     if env and env.isdigit() and int(env) > 0:
         return int(env)
     return max(1, min(16, os.cpu_count() or 1))
+
+
+def dump_outputs(out_dir: str, rank: int, arrays: dict) -> None:
+    """--dump-outputs: each array of `arrays` (name -> 1-D integer numpy array) as
+    out_dir/<name>.npy in float64 (exact for the int32 / uint32 / uint8 outputs), rank r > 0's
+    as <name>.rank<r>.npy. All arrays together stay within DUMP_BUDGET: a longer array is cut
+    to a sample of its rows (sorted indices from a fixed seed, the same for every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = (DUMP_BUDGET // max(len(arrays), 1) - 128) // 8  # (128: a .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if len(a) > rows:
+            a = a[np.sort(np.random.default_rng(0x5EED).choice(len(a), rows, replace=False))]
+        suffix = f".rank{rank}" if rank else ""
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a.astype(np.float64))
 
 
 def cpu_model() -> str:
@@ -273,10 +305,11 @@ def build_table(keys_np, fids_np, t_size, load_factor, dev, sp, rank, world):
     return table, slots
 
 
-def timed(step, ws, args, world, stream, dev, before=None, after=None):
-    """W warmup steps, then exactly K steps between barrier + synchronize; then the same K steps
-    again with the library's hipEvents around its kernels. Max over ranks of (wall s, GPU ms,
-    main-kernel ms per call, rest ms per call)."""
+def timed(step, ws, args, world, stream, dev, before=None, after=None, dump=None):
+    """W warmup steps, then exactly K steps between barrier + synchronize; with --full then the
+    same K steps again with the library's hipEvents around its kernels. Max over ranks of (wall
+    s, GPU ms, main-kernel ms per call, rest ms per call); a plain run has no per-kernel times.
+    dump (a --dump-outputs run's writer) is called right after the timed steps."""
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -298,11 +331,15 @@ def timed(step, ws, args, world, stream, dev, before=None, after=None):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     gpu_ms = ev0.elapsed_time(ev1)
-    ws.timing(True)
-    for _ in range(args.steps):
-        step()
-    n_t, phases = ws.phases_read()
-    ws.timing(False)
+    if dump is not None:
+        dump()
+    phases, n_t = {}, 0
+    if args.full:
+        ws.timing(True)
+        for _ in range(args.steps):
+            step()
+        n_t, phases = ws.phases_read()
+        ws.timing(False)
     names = list(phases)
     mine = [elapsed, gpu_ms] + [phases[k] / max(n_t, 1) for k in names]
     stats = torch.tensor(mine, dtype=torch.float64, device=dev)
@@ -473,9 +510,17 @@ def bench_contigs(args, rank, world, dev, stream, sp):
                                          n_bases, 11, d_hits.data_ptr(), cap, d_nh.data_ptr(),
                                          0, 0, sp)
 
-    elapsed, gpu_ms, ph = timed(step, ws, args, world, stream, dev)
+    def dump():
+        n = min(int(d_nh.item()), cap)
+        hits = d_hits.cpu().numpy().view(kmeranno.HIT_DTYPE)[:n]
+        dump_outputs(args.dump_outputs, rank, {
+            "n_hits": np.array([n], np.int64),
+            **{f"hit_{f}": hits[f] for f in ("contig", "left", "fid", "strand", "frame")}})
+
+    elapsed, gpu_ms, ph = timed(step, ws, args, world, stream, dev,
+                                dump=dump if args.dump_outputs else None)
     # one kernel since round 4 (hits emitted by the probe); older libraries: + the emit pass
-    k_ms, rest_ms = ph["contigs_probe_kernel"], ph.get("scan_emit", 0.0)
+    k_ms, rest_ms = ph["contigs_probe_kernel"] if args.full else None, ph.get("scan_emit", 0.0)
     n_hits = int(d_nh.item())
     assert n_hits <= cap, "hit buffer too small"
     if rank == 0:
@@ -496,13 +541,15 @@ def bench_contigs(args, rank, world, dev, stream, sp):
                        "parallelism": f"genome-shard x{world}" + collective_note(args, world)},
             "seqs_per_s": n_contig * args.steps * world / elapsed,
             "gpu_ms_per_step": gpu_ms / args.steps,
-            "phases_ms": {"probe": k_ms, **({"scan_emit": rest_ms} if "scan_emit" in ph else {})},
-            # 6-frame probe: one 64-B bucket per probed window, 1 B per base, 16 B per hit
-            "roofline": roofline("probed windows x 64 B + bases + hits x 16 B", "c3",
-                                 f"{kname} (6-frame translate + 2 probes per base)", k_ms,
-                                 n_probe * BYTES_PER_LOOKUP + n_bases + 16 * n_hits,
-                                 table.info.bytes, n_probe),
         }
+        if args.full:
+            out["phases_ms"] = {"probe": k_ms,
+                                **({"scan_emit": rest_ms} if "scan_emit" in ph else {})}
+            # 6-frame probe: one 64-B bucket per probed window, 1 B per base, 16 B per hit
+            out["roofline"] = roofline("probed windows x 64 B + bases + hits x 16 B", "c3",
+                                       f"{kname} (6-frame translate + 2 probes per base)", k_ms,
+                                       n_probe * BYTES_PER_LOOKUP + n_bases + 16 * n_hits,
+                                       table.info.bytes, n_probe)
         if world > 1:
             add_rank_fields(out, table, args)
         if world == 1 and not args.no_cpu_baseline:
@@ -800,9 +847,17 @@ def main():
                     help="override the workload's proteins per rank (tuning runs only)")
     ap.add_argument("--table-rows", type=int, default=0,
                     help="override the workload's table rows (tests and tuning runs only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, also measure the per-kernel times (a second "
+                         "pass of the steps), the roofline with its live gather ceiling, the "
+                         "host-path (e2e) call and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the gather ceiling and the host-path (e2e) measurement")
+                    help="with --full: skip the gather ceiling and the host-path (e2e) "
+                         "measurement")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
                     help="collectives: nccl = RCCL over xGMI (one GPU per rank); gloo = host-"
                          "staged, to rehearse several ranks on one GPU (with --same-device)")
@@ -822,12 +877,16 @@ def main():
                     help="after timing, check the multi-rank outputs, tally and table against "
                          "single-rank calls on rank 0 (exit 1 on a mismatch)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps alone
+        args.no_extras = args.no_cpu_baseline = True
 
     kmeranno.set_option(kmeranno.OPT_PACKED_INPUT, args.packed_input)
     kmeranno.set_option(kmeranno.OPT_PLACEMENT, 0 if args.placement == "chained" else -1)
     for o in args.option:
         name, _, value = o.partition("=")
         kmeranno.set_option(kmeranno._OPT_NAMES[name], int(value))
+    if args.dump_outputs and args.workload in ("genomes", "fasta"):
+        ap.error("--dump-outputs: the command-level workloads write reports, not arrays")
     if args.workload == "genomes":  # a command-level run: `kma apply` as a child process
         bench_genomes(args)
         return
@@ -862,9 +921,15 @@ def main():
     t_size = args.table_rows or t_size
     strong = args.workload == "c4"
     t0 = time.perf_counter()
-    sig = synth.make_table(t_size, n_fid, seed, K, protos_only=rank != 0)
     qseed = seed * 1_000_003 + 17 + (0 if strong else rank)
-    residues, offsets, _, _ = synth.make_queries(sig, n_seq, qseed)
+    # the build's stored copy of these very arrays where it has one (c5 on one rank), else the
+    # generator
+    sig = synth_cache.load_table(t_size, n_fid, seed, K) if rank == 0 else None
+    queries = synth_cache.load_queries(t_size, n_fid, seed, K, n_seq, qseed)
+    source = "generated" if sig is None or queries is None else "read from the build's copy"
+    if sig is None:
+        sig = synth.make_table(t_size, n_fid, seed, K, protos_only=rank != 0)
+    residues, offsets, _, _ = queries or synth.make_queries(sig, n_seq, qseed)
     batch_windows = int(np.maximum(np.diff(offsets).astype(np.int64) - K + 1, 0).sum())
     batch_seqs = len(offsets) - 1
     lo = 0
@@ -875,7 +940,7 @@ def main():
     lens = np.diff(offsets).astype(np.int64)
     n_win = int(np.maximum(lens - K + 1, 0).sum())
     log(f"[rank {rank}] workload {args.workload}: {t_size} table rows, {n_seq} proteins "
-        f"(from {lo}), {n_win} windows, generated in {time.perf_counter() - t0:.1f}s")
+        f"(from {lo}), {n_win} windows, {source} in {time.perf_counter() - t0:.1f}s")
     table, slots = build_table(sig.keys, sig.fids, t_size, args.load_factor, dev, sp, rank, world)
     n_res = int(offsets[-1] - offsets[0])
     ws = kmeranno.Workspace(local, n_res)
@@ -900,8 +965,13 @@ def main():
             kdist.reduce_tallies(d_tally, dst=0)
         job_tally.copy_(d_tally)
 
+    def dump():  # what a caller of the device entry point holds after the last timed step
+        dump_outputs(args.dump_outputs, rank, {
+            "fid": d_fid.cpu().numpy(), "count": d_cnt.cpu().numpy(),
+            "status": d_st.cpu().numpy(), "tally": job_tally.cpu().numpy()})
+
     elapsed, gpu_ms, ph = timed(step, ws, args, world, stream, dev, before=d_tally.zero_,
-                                after=reduce)
+                                after=reduce, dump=dump if args.dump_outputs else None)
     st = d_st.cpu().numpy()
     called = int((st == kmeranno.STATUS_CALLED).sum())
     verify = None
@@ -937,11 +1007,13 @@ def main():
             "seqs_per_s": seqs * args.steps / elapsed,
             "called_per_batch": called,
             "gpu_ms_per_step": gpu_ms / args.steps,
-            "phases_ms": ph,
         }
-        wl_tag = args.workload if args.load_factor == 0.5 else f"{args.workload}_lf{args.load_factor:g}"
-        out["roofline"] = protein_roofline(ph, wl_tag, m, n_win, n_res, table.info.bytes,
-                                           live=not args.no_extras)
+        if args.full:
+            out["phases_ms"] = ph
+            wl_tag = (args.workload if args.load_factor == 0.5
+                      else f"{args.workload}_lf{args.load_factor:g}")
+            out["roofline"] = protein_roofline(ph, wl_tag, m, n_win, n_res, table.info.bytes,
+                                               live=not args.no_extras)
         if world > 1:
             add_rank_fields(out, table, args)
         if world == 1:

@@ -8,7 +8,7 @@ OUT=gpurun_out/$1; WL=$2; shift 2; mkdir -p $OUT; T=${TAG:+_$TAG}
 for rep in 1 2; do
   for lib in default "$@"; do
     if [ $lib = default ]; then unset KMERANNO_LIB; else export KMERANNO_LIB=kmers.anno_amd/build/$lib/libkmeranno.so; fi
-    timeout -k 10 300 python bench.py --workload $WL --no-cpu-baseline --no-extras $EXTRA > $OUT/${WL}${T}_${lib}_r$rep.json 2> $OUT/${WL}${T}_${lib}_r$rep.log
+    timeout -k 10 300 python bench.py --full --workload $WL --no-cpu-baseline --no-extras $EXTRA > $OUT/${WL}${T}_${lib}_r$rep.json 2> $OUT/${WL}${T}_${lib}_r$rep.log
     rc=$?; echo "$WL$T $lib r$rep rc=$rc" >> $OUT/steps.log; [ $rc = 0 ] || exit $rc
   done
 done

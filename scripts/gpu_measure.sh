@@ -27,29 +27,29 @@ for s in $SECTIONS; do
         step pmc_gather_$tag 120 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_gather_$tag -o run -- $GB 1536 quad 4
         for wl in ${WLS:-c5 c2 c3 c4}; do  # c5_lf0.75: c5 at load factor 0.75 (LF sweep lines)
           wa="--workload ${wl%%_lf*}"; [ "$wl" != "${wl#*_lf}" ] && wa="$wa --load-factor ${wl#*_lf}"
-          step pmc_${wl}_$tag 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_${wl}_$tag -o run -- python3 bench.py $SHORT $wa
+          step pmc_${wl}_$tag 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_${wl}_$tag -o run -- python3 bench.py --full $SHORT $wa
         done
       done
       step traffic 60 python3 scripts/traffic_summary.py $OUT 8388608
       cp $OUT/traffic.log ${TRAFFIC:-$OUT/traffic.json} ;;
     stats)
-      step stats_c5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c5 -o run -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras
-      step stats_c3 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c3 -o run -- python3 bench.py --workload c3 --steps 20 --warmup 3 --no-cpu-baseline --no-extras ;;
+      step stats_c5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c5 -o run -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras
+      step stats_c3 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c3 -o run -- python3 bench.py --full --workload c3 --steps 20 --warmup 3 --no-cpu-baseline --no-extras ;;
     bench)
-      step bench_c5 600 python3 bench.py
-      step bench_c2 300 python3 bench.py --workload c2 --no-cpu-baseline
-      step bench_c3 300 python3 bench.py --workload c3 --no-cpu-baseline
-      step bench_c4 300 python3 bench.py --workload c4 --no-cpu-baseline ;;
+      step bench_c5 600 python3 bench.py --full
+      step bench_c2 300 python3 bench.py --full --workload c2 --no-cpu-baseline
+      step bench_c3 300 python3 bench.py --full --workload c3 --no-cpu-baseline
+      step bench_c4 300 python3 bench.py --full --workload c4 --no-cpu-baseline ;;
     lf)  # c5 load-factor sweep lines (their PMC requests per window: WLS with c5_lf0.75 c5_lf0.9)
       for lf in 0.75 0.9; do
-        step bench_c5_lf$lf 600 python3 bench.py --workload c5 --load-factor $lf --no-cpu-baseline
+        step bench_c5_lf$lf 600 python3 bench.py --full --workload c5 --load-factor $lf --no-cpu-baseline
       done ;;
     sq)
       P1="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS"
       P2="SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_WAIT_INST_LDS SQ_INSTS_SMEM GRBM_GUI_ACTIVE"
       for wl in ${SQ_WLS:-c5 c3}; do
-        step sq_${wl}_p1 300 rocprofv3 --pmc $P1 --kernel-trace --output-format csv -d $OUT/sq_${wl}_p1 -o run -- python3 bench.py $SHORT --workload $wl
-        step sq_${wl}_p2 300 rocprofv3 --pmc $P2 --kernel-trace --output-format csv -d $OUT/sq_${wl}_p2 -o run -- python3 bench.py $SHORT --workload $wl
+        step sq_${wl}_p1 300 rocprofv3 --pmc $P1 --kernel-trace --output-format csv -d $OUT/sq_${wl}_p1 -o run -- python3 bench.py --full $SHORT --workload $wl
+        step sq_${wl}_p2 300 rocprofv3 --pmc $P2 --kernel-trace --output-format csv -d $OUT/sq_${wl}_p2 -o run -- python3 bench.py --full $SHORT --workload $wl
       done
       step sq_summary 60 python3 scripts/sq_summary.py $OUT ;;
   esac

@@ -10,7 +10,7 @@ for rep in 1 2; do
   for set in "$@"; do
     i=$((i + 1)); args=()
     [ "$set" = "-" ] || for o in $set; do args+=(--option "$o"); done
-    timeout -k 10 300 python bench.py --workload $WL --no-cpu-baseline --no-extras "${args[@]}" \
+    timeout -k 10 300 python bench.py --full --workload $WL --no-cpu-baseline --no-extras "${args[@]}" \
       > $OUT/${WL}_s${i}_r$rep.json 2> $OUT/${WL}_s${i}_r$rep.log
     rc=$?; echo "$WL s$i [$set] r$rep rc=$rc" >> $OUT/steps.log; [ $rc = 0 ] || exit $rc
   done

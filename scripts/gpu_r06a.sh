@@ -11,14 +11,14 @@ if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 for rep in 1 2; do
   for arm in mod random; do
     X=""; [ $arm = random ] && X="--option layout=6"
-    timeout -k 10 300 python bench.py --workload c5 --no-cpu-baseline --no-extras $X > $OUT/c5_${arm}_r$rep.json 2> $OUT/c5_${arm}_r$rep.log
+    timeout -k 10 300 python bench.py --full --workload c5 --no-cpu-baseline --no-extras $X > $OUT/c5_${arm}_r$rep.json 2> $OUT/c5_${arm}_r$rep.log
     r=$?; echo "c5 $arm r$rep rc=$r" >> $OUT/steps.log; [ $r = 0 ] || exit $r
   done
 done
 for rep in 1 2; do
   for arm in block4 wave1 wave2; do
     X=""; [ $arm = wave1 ] && X="--option block_waves=1"; [ $arm = wave2 ] && X="--option block_waves=1 --option block_proteins=2"
-    timeout -k 10 300 python bench.py --workload c2 --no-cpu-baseline --no-extras $X > $OUT/c2_${arm}_r$rep.json 2> $OUT/c2_${arm}_r$rep.log
+    timeout -k 10 300 python bench.py --full --workload c2 --no-cpu-baseline --no-extras $X > $OUT/c2_${arm}_r$rep.json 2> $OUT/c2_${arm}_r$rep.log
     r=$?; echo "c2 $arm r$rep rc=$r" >> $OUT/steps.log; [ $r = 0 ] || exit $r
   done
 done

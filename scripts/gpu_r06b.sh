@@ -15,7 +15,7 @@ for rep in 1 2; do
     X=""; unset KMERANNO_LIB
     [ $arm = random ] && X="--option layout=6"
     [ $arm = modopen ] && export KMERANNO_LIB=kmers.anno_amd/build/modopen/libkmeranno.so
-    timeout -k 10 300 python bench.py --workload c5 --no-cpu-baseline --no-extras $X > $OUT/c5_${arm}_r$rep.json 2> $OUT/c5_${arm}_r$rep.log
+    timeout -k 10 300 python bench.py --full --workload c5 --no-cpu-baseline --no-extras $X > $OUT/c5_${arm}_r$rep.json 2> $OUT/c5_${arm}_r$rep.log
     r=$?; echo "c5 $arm r$rep rc=$r" >> $OUT/steps.log; [ $r = 0 ] || exit $r
   done
 done

@@ -14,7 +14,7 @@ for rep in 1 2; do
   for wl in c5 c4 c2; do
     for arm in default adj; do
       if [ $arm = adj ]; then export KMERANNO_LIB=kmers.anno_amd/build/adj/libkmeranno.so; else unset KMERANNO_LIB; fi
-      timeout -k 10 300 python bench.py --workload $wl --no-cpu-baseline --no-extras > $OUT/${wl}_${arm}_r$rep.json 2> $OUT/${wl}_${arm}_r$rep.log
+      timeout -k 10 300 python bench.py --full --workload $wl --no-cpu-baseline --no-extras > $OUT/${wl}_${arm}_r$rep.json 2> $OUT/${wl}_${arm}_r$rep.log
       r=$?; echo "$wl $arm r$rep rc=$r" >> $OUT/steps.log; [ $r = 0 ] || exit $r
     done
   done

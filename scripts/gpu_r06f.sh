@@ -15,14 +15,14 @@ for rep in 1 2; do
     [ $rep = 2 ] && [ $wl = c5_lf0.9 ] && continue
     for arm in t3 t1; do
       if [ $arm = t1 ]; then export KMERANNO_LIB=kmers.anno_amd/build/t1/libkmeranno.so; else unset KMERANNO_LIB; fi
-      timeout -k 10 300 python bench.py $wa --no-cpu-baseline --no-extras > $OUT/${wl}_${arm}_r$rep.json 2> $OUT/${wl}_${arm}_r$rep.log
+      timeout -k 10 300 python bench.py --full $wa --no-cpu-baseline --no-extras > $OUT/${wl}_${arm}_r$rep.json 2> $OUT/${wl}_${arm}_r$rep.log
       r=$?; echo "$wl $arm r$rep rc=$r" >> $OUT/steps.log; [ $r = 0 ] || exit $r
     done
   done
 done
 for arm in t3 t1; do
   if [ $arm = t1 ]; then export KMERANNO_LIB=kmers.anno_amd/build/t1/libkmeranno.so; else unset KMERANNO_LIB; fi
-  timeout -k 10 300 python bench.py --workload c5 --no-cpu-baseline --no-extras > $OUT/c5_${arm}_r3.json 2> $OUT/c5_${arm}_r3.log
+  timeout -k 10 300 python bench.py --full --workload c5 --no-cpu-baseline --no-extras > $OUT/c5_${arm}_r3.json 2> $OUT/c5_${arm}_r3.log
   r=$?; echo "c5 $arm r3 rc=$r" >> $OUT/steps.log; [ $r = 0 ] || exit $r
 done
 python3 - "$OUT" <<'PY'

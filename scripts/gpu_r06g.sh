@@ -12,7 +12,7 @@ for rep in 1 2; do
   for wl in c5 c4 c2 c3; do
     for arm in base new; do
       if [ $arm = base ]; then export KMERANNO_LIB=kmers.anno_amd/build/base/libkmeranno.so; else unset KMERANNO_LIB; fi
-      timeout -k 10 300 python bench.py --workload $wl --no-cpu-baseline --no-extras > $OUT/${wl}_${arm}_r$rep.json 2> $OUT/${wl}_${arm}_r$rep.log
+      timeout -k 10 300 python bench.py --full --workload $wl --no-cpu-baseline --no-extras > $OUT/${wl}_${arm}_r$rep.json 2> $OUT/${wl}_${arm}_r$rep.log
       r=$?; echo "$wl $arm r$rep rc=$r" >> $OUT/steps.log; [ $r = 0 ] || exit $r
     done
   done

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${1:-r06k}; mkdir -p $OUT
 for rep in 1 2; do
   for bp in 6 7 5 8; do
-    timeout -k 10 300 python bench.py --workload c5 --no-cpu-baseline --no-extras --option block_proteins=$bp > $OUT/c5_bp${bp}_r$rep.json 2> $OUT/c5_bp${bp}_r$rep.log
+    timeout -k 10 300 python bench.py --full --workload c5 --no-cpu-baseline --no-extras --option block_proteins=$bp > $OUT/c5_bp${bp}_r$rep.json 2> $OUT/c5_bp${bp}_r$rep.log
     r=$?; echo "c5 bp$bp r$rep rc=$r" >> $OUT/steps.log; [ $r = 0 ] || exit $r
   done
 done

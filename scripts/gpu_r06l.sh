@@ -9,7 +9,7 @@ for rep in 1 2; do
   for wl in c4 c2; do
     for arm in p4 p8; do
       if [ $arm = p8 ]; then export KMERANNO_LIB=kmers.anno_amd/build/cap8/libkmeranno.so; else unset KMERANNO_LIB; fi
-      timeout -k 10 300 python bench.py --workload $wl --no-cpu-baseline --no-extras > $OUT/${wl}_${arm}_r$rep.json 2> $OUT/${wl}_${arm}_r$rep.log
+      timeout -k 10 300 python bench.py --full --workload $wl --no-cpu-baseline --no-extras > $OUT/${wl}_${arm}_r$rep.json 2> $OUT/${wl}_${arm}_r$rep.log
       r=$?; echo "$wl $arm r$rep rc=$r" >> $OUT/steps.log; [ $r = 0 ] || exit $r
     done
   done
