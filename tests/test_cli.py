@@ -218,11 +218,53 @@ def test_kma_apply_errors(kma_bin, apply_inputs, tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("k", [8, 10])
+def test_kma_apply_fasta_k5_kmerdb(kma_bin, oracle_c, tmp_path):
+    """`kma apply-fasta` against a kmerdb.tbl of K = 5 rows (tests/test_gpu_narrow_k.py's table;
+    the last row sets the logged kmer size, ApplyKmerProcessor.java:108-109) with 8-residue rows
+    in between: the log says "Kmer size is 5", and the reports equal the oracle's calls for the
+    protein extractor's own K = 8 (ProteinKmers keeps its default size, :123), to which the
+    5-residue rows are rows of another length; only the 8-residue ones call proteins."""
+    from test_gpu_narrow_k import ROLE_ALPHABETS, narrow_workload
+    wl = narrow_workload(5)
+    names = [f"Role{a}" for a in ROLE_ALPHABETS]
+    long_single = [j for j, p in enumerate(wl.prots) if wl.kinds[j] == 0 and len(p) >= 120][:40]
+    rows = list(wl.rows)
+    for j in long_single:  # 8 windows of the protein under the role of its first residue
+        p = wl.prots[j]
+        role = [p[0] in a for a in ROLE_ALPHABETS].index(True)
+        for i in range(0, 8 * 11, 11):
+            rows.insert((len(rows) * (i + 1)) // 100, (p[i:i + 8], role))
+    assert len(rows[-1][0]) == 5
+    (tmp_path / "kmerdb.tbl").write_text("".join(f"{km}\t{names[f]}\n" for km, f in rows))
+    (tmp_path / "roles.in.use").write_text("".join(f"{n}\trole {n}\n" for n in names[:3]))
+    ids = [f"fig|5.5.peg.{j + 1}" for j in range(len(wl.prots))]
+    (tmp_path / "5.5.faa").write_text("".join(
+        f">{i} protein {j}\n{p}\n" for j, (i, p) in enumerate(zip(ids, wl.prots))))
+    ot = oracle_c.Table([km for km, _ in rows], [f for _, f in rows])
+    fid, cnt, st = oracle_c.apply(ot, wl.res, wl.off, 8, 5, 0)
+    called = np.flatnonzero(st == 1)
+    assert len(called) >= len(long_single) == 40
+    verify = ["genome_id\tpeg_id\trole\thits\tfunction"] + [
+        f"5.5\t{ids[j]}\t{names[fid[j]]}\t{int(cnt[j])}\tprotein {j}" for j in called]
+    apply = ["5.5\t" + "\t".join(str(int((fid[called] == f).sum())) for f in range(3))]
+    base = [kma_bin, "apply-fasta", str(tmp_path / "kmerdb.tbl"), str(tmp_path / "roles.in.use"),
+            str(tmp_path / "5.5.faa")]
+    out = subprocess.run(base, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    assert "Kmer size is 5." in out.stderr
+    assert out.stdout.splitlines() == verify
+    out = subprocess.run(base[:2] + ["--format", "APPLY"] + base[2:], capture_output=True,
+                         text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.splitlines() == apply
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [5, 8, 10])
 def test_kma_contigs_report(kma_bin, oracle_c, small_gto, apply_inputs, tmp_path, k):
     """`kma contigs` (6-frame kmers of every genome's contigs probed against a kmer database
-    whose last row sets K, as ApplyKmerProcessor.java:108 / KmerProcessor -K do) at K = 8 and
-    K = 10 (a wide table): every line equals the oracle's hit (KmerReference.java:157-203)."""
+    whose last row sets K, as ApplyKmerProcessor.java:108 / KmerProcessor -K do) at K = 5, K = 8
+    and K = 10 (a wide table): every line equals the oracle's hit (KmerReference.java:157-203)."""
     d, _, _, _ = apply_inputs
     contigs = [c["dna"] for c in small_gto["contigs"]]
     dna, off = oracle_c.pack_strings(contigs)

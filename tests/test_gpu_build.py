@@ -34,10 +34,10 @@ def _family_proteins(rng, n_fam=80, n=1500):
 
 
 @pytest.mark.parametrize("flags", [0, 1])
-@pytest.mark.parametrize("k", [8, 10, 12])
+@pytest.mark.parametrize("k", [5, 8, 10, 12])
 def test_build_signatures_vs_oracle(kma, oracle_c, flags, k):
     """The discriminating (kmer, role) rows equal the oracle's, in key order without
-    duplicates, at K = 8 and the wide sizes (BuildKmerProcessor -K, :84-87); a window with a
+    duplicates, at K = 5, K = 8 and the wide sizes (BuildKmerProcessor -K, :84-87); a window with a
     byte outside A-Z/'*' is refused (KMA_E_ALPHABET)."""
     rng = np.random.default_rng(17 + flags + k)
     prots, roles = _family_proteins(rng)
