@@ -463,6 +463,51 @@ int kma_propose_pegs(const kma_hit* hits, uint64_t n_hits, const uint32_t* peg_l
                      double min_fuzz, int device, kma_proposal* out, uint64_t cap,
                      uint64_t* n_out, uint64_t* stats);
 
+/* ---- ORF extension of the proposals (added under ABI 7) --------------------------------------
+ * PegProposalList.propose (locations/PegProposalList.java:67-77) first grows every proposal to
+ * the ORF around it (PegProposal.create -> Location.extend(genome), PegProposal.java:50-58),
+ * then drops it when it is weak or small. Both ends of the ORF depend on the genome alone, so
+ * they are precomputed: kma_orf_index_create (added under ABI 7) classifies every codon of both
+ * strands of the new genome on `device` and runs two segmented scans per (contig, strand,
+ * frame) — the next in-frame stop at or after a position, and the farthest start codon since
+ * the previous in-frame stop — into two int32 arrays (about 16 device bytes per base; the DNA
+ * is not kept). The index is built once per new genome; kma_extend_proposals (added under ABI
+ * 7) then answers every proposal of every close genome with two loads, whatever the ORF's
+ * length. kma_orf_index_destroy (added under ABI 7) frees it; NULL is allowed.
+ *
+ * Location.extend is external (org.theseed:shared) and parity-unpinned; restated, as in
+ * kmeranno/projector.py and oracle/proposal_list.py (the three must agree): in strand
+ * coordinates ('+': a = left - 1, b = right - 1; '-': on the reverse complement of the contig
+ * of n bases, a = n - right, b = n - left; a < 0 or b >= n: rejected) the stop is the first
+ * in-frame stop codon at or after the span's last whole codon a + ((b - a + 1) / 3 - 1) * 3,
+ * that codon included (no whole stop codon before the contig end: rejected); the start is the
+ * farthest-upstream ATG / GTG / TTG at or before a with no in-frame stop between it and a, the
+ * codon at a examined first (a stop there, or no start: rejected). DNA is case-insensitive; a
+ * base outside ACGT never forms a start or a stop on either strand. Stops: TAA TAG TGA for
+ * genetic codes 1 and 11, TAA TAG for code 4; any other code is KMA_E_INVALID.
+ *
+ * kma_extend_proposals: all buffers are host buffers; synchronous. Entry i of the outputs
+ * describes proposal i (nothing is compacted or reordered: the TreeSet downstream depends on
+ * insertion order). out_left / out_right: the extended 1-based forward-strand edges, 0 / 0 for
+ * KMA_ORF_REJECTED. The filters run in the reference's order (PegProposalList.java:71-76):
+ * rejected, then weak ((double) evidence / (right - left + 1) < min_strength; the caller passes
+ * the DNA strength, minStrength / 3), then small (evidence < min_evidence). stats[4]: made (= n),
+ * rejected, weak, small. n == 0: KMA_OK, stats zeroed, no device touched. KMA_E_INVALID: a
+ * proposal with contig >= n_contig, a strand other than '+' / '-' or right - left + 1 < 3;
+ * 2^31 or more bases; null arguments. The index is immutable: concurrent calls on one index are
+ * allowed (each allocates and frees its own staging).                                          */
+typedef struct kma_orf_index kma_orf_index; /* opaque: one genome's stop/start scans on one GPU */
+int kma_orf_index_create(const uint8_t* dna, const uint64_t* offsets, uint32_t n_contig,
+                         int genetic_code, int device, kma_orf_index** out);
+int kma_orf_index_destroy(kma_orf_index* idx);
+#define KMA_ORF_KEPT 0     /* extended, strong enough, enough evidence                         */
+#define KMA_ORF_REJECTED 1 /* Location.extend gave null (rejectedCount)                         */
+#define KMA_ORF_WEAK 2     /* (double) evidence / length < min_strength (weakCount)             */
+#define KMA_ORF_SMALL 3    /* evidence < min_evidence (smallCount)                              */
+int kma_extend_proposals(const kma_orf_index* idx, const kma_proposal* props, uint64_t n,
+                         double min_strength, int min_evidence, int32_t* out_left,
+                         int32_t* out_right, uint8_t* out_status, uint64_t* stats);
+
 /* ---- hash annotator scoring (HashAnnotationProcessor.java:221-328) ---------------------------
  * A genome's distinct protein sequences (the caller keys features by MD5, as GenomeProteinKmers
  * does; proteins holding '*' are left out, :239-241) against the prototypes of the role

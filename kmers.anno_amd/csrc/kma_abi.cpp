@@ -31,6 +31,7 @@
 #include "kma_distance.h"
 #include "kma_hashanno.h"
 #include "kma_internal.h"
+#include "kma_orf.h"
 #include "kma_pack.h"
 #include "kma_tsv.h"
 
@@ -2695,6 +2696,139 @@ int kma_propose_pegs(const kma_hit* hits, uint64_t n_hits, const uint32_t* peg_l
   if (stats[3] > cap)
     return fail(KMA_E_CAPACITY, "%llu proposals, capacity %llu", (unsigned long long)stats[3],
                 (unsigned long long)cap);
+  return KMA_OK;
+}
+
+}  // extern "C"
+
+// ---- ORF index of the projector (kma_orf.hip) ---------------------------------------------------
+// One genome's stop / start scans on one device. Immutable after creation: kma_extend_proposals
+// only reads it and stages every call in buffers of its own, so calls may run concurrently.
+struct kma_orf_index {
+  int device = 0;
+  uint32_t n_contig = 0;
+  int32_t* len = nullptr;      // device: n_contig contig lengths
+  uint64_t* hoff = nullptr;    // device: n_contig + 1 per-strand slot offsets
+  uint32_t* stop_at = nullptr; // device: 2 hoff[n_contig] words each
+  uint32_t* start_at = nullptr;
+  ~kma_orf_index() {
+    for (void* p : {(void*)len, (void*)hoff, (void*)stop_at, (void*)start_at})
+      if (p) (void)hipFree(p);
+  }
+};
+
+extern "C" {
+
+int kma_orf_index_create(const uint8_t* dna, const uint64_t* offsets, uint32_t n_contig,
+                         int genetic_code, int device, kma_orf_index** out) {
+  if (!out) return fail(KMA_E_INVALID, "null argument");
+  *out = nullptr;
+  if (!offsets) return fail(KMA_E_INVALID, "null argument");
+  if (genetic_code != 1 && genetic_code != 4 && genetic_code != 11)
+    return fail(KMA_E_INVALID, "genetic code %d: the ORF index knows codes 1, 4 and 11",
+                genetic_code);
+  std::vector<uint64_t> off(n_contig + 1ull), hoff(n_contig + 1ull);
+  std::vector<int32_t> len(n_contig);
+  for (uint32_t c = 0; c < n_contig; ++c) {
+    if (offsets[c + 1] < offsets[c]) return fail(KMA_E_INVALID, "offsets decrease at %u", c);
+    if (offsets[c + 1] - offsets[0] >= (1ull << 31))
+      return fail(KMA_E_INVALID, "2^31 bases or more");
+    off[c + 1] = offsets[c + 1] - offsets[0];
+    len[c] = (int32_t)(offsets[c + 1] - offsets[c]);
+    hoff[c + 1] = hoff[c] + 3ull * kma::orf_frame_slots((uint32_t)len[c]);
+  }
+  const uint64_t total = off[n_contig], half = hoff[n_contig];
+  if (total && !dna) return fail(KMA_E_INVALID, "null argument");
+  DeviceScope ds(device);
+  if (ds.err != hipSuccess) return fail(KMA_E_DEVICE, "hipSetDevice(%d): %s", device,
+                                        hipGetErrorString(ds.err));
+  std::unique_ptr<kma_orf_index> idx(new kma_orf_index);
+  idx->device = device;
+  idx->n_contig = n_contig;
+  KMA_HIP(hipMalloc(&idx->len, std::max<size_t>(n_contig * 4ull, 4)));
+  KMA_HIP(hipMalloc(&idx->hoff, (n_contig + 1ull) * 8));
+  KMA_HIP(hipMalloc(&idx->stop_at, std::max<size_t>(half * 8, 4)));
+  KMA_HIP(hipMalloc(&idx->start_at, std::max<size_t>(half * 8, 4)));
+  DevBufs b;  // the DNA and the scans' scratch live for the build only
+  uint8_t* d_dna;
+  uint64_t* d_off;
+  KMA_HIP(b.alloc(&d_dna, total));
+  KMA_HIP(b.alloc(&d_off, (n_contig + 1ull) * 8));
+  kma::OrfBuildArgs a{};
+  a.dna = d_dna;
+  a.offsets = d_off;
+  a.hoff = idx->hoff;
+  a.n_contig = n_contig;
+  a.half = half;
+  a.stops = genetic_code == 4 ? kma::kOrfStops2 : kma::kOrfStops3;
+  a.stop_at = idx->stop_at;
+  a.start_at = idx->start_at;
+  size_t tb = 0;
+  KMA_HIP(kma::launch_orf_build(a, nullptr, &tb, nullptr));
+  void* d_temp;
+  KMA_HIP(b.alloc(&d_temp, tb));
+  if (total) KMA_HIP(hipMemcpy(d_dna, dna + offsets[0], total, hipMemcpyHostToDevice));
+  KMA_HIP(hipMemcpy(d_off, off.data(), (n_contig + 1ull) * 8, hipMemcpyHostToDevice));
+  KMA_HIP(hipMemcpy(idx->hoff, hoff.data(), (n_contig + 1ull) * 8, hipMemcpyHostToDevice));
+  if (n_contig) KMA_HIP(hipMemcpy(idx->len, len.data(), n_contig * 4ull, hipMemcpyHostToDevice));
+  KMA_HIP(kma::launch_orf_build(a, d_temp, &tb, nullptr));
+  KMA_HIP(hipStreamSynchronize(nullptr));
+  *out = idx.release();
+  return KMA_OK;
+}
+
+int kma_orf_index_destroy(kma_orf_index* idx) {
+  if (!idx) return KMA_OK;
+  DeviceScope ds(idx->device);
+  delete idx;
+  return KMA_OK;
+}
+
+int kma_extend_proposals(const kma_orf_index* idx, const kma_proposal* props, uint64_t n,
+                         double min_strength, int min_evidence, int32_t* out_left,
+                         int32_t* out_right, uint8_t* out_status, uint64_t* stats) {
+  if (!idx || !stats) return fail(KMA_E_INVALID, "null argument");
+  stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (n == 0) return KMA_OK;
+  if (!props || !out_left || !out_right || !out_status)
+    return fail(KMA_E_INVALID, "null argument");
+  for (uint64_t i = 0; i < n; ++i) {
+    const kma_proposal& p = props[i];
+    if (p.contig >= idx->n_contig)
+      return fail(KMA_E_INVALID, "proposal %llu: contig %u >= %u", (unsigned long long)i,
+                  p.contig, idx->n_contig);
+    if (p.strand != '+' && p.strand != '-')
+      return fail(KMA_E_INVALID, "proposal %llu: strand must be '+' or '-'",
+                  (unsigned long long)i);
+    if ((int64_t)p.right - p.left + 1 < 3)
+      return fail(KMA_E_INVALID, "proposal %llu: shorter than a codon", (unsigned long long)i);
+  }
+  DeviceScope ds(idx->device);
+  if (ds.err != hipSuccess) return fail(KMA_E_DEVICE, "hipSetDevice(%d): %s", idx->device,
+                                        hipGetErrorString(ds.err));
+  DevBufs b;
+  kma_proposal* d_props;
+  kma::OrfExtendArgs a{};
+  KMA_HIP(b.alloc(&d_props, n * sizeof(kma_proposal)));
+  KMA_HIP(b.alloc(&a.left, n * 4));
+  KMA_HIP(b.alloc(&a.right, n * 4));
+  KMA_HIP(b.alloc(&a.status, n));
+  KMA_HIP(b.alloc(&a.stats, 32));
+  a.len = idx->len;
+  a.hoff = idx->hoff;
+  a.stop_at = idx->stop_at;
+  a.start_at = idx->start_at;
+  a.props = d_props;
+  a.n = n;
+  a.min_strength = min_strength;
+  a.min_evidence = min_evidence;
+  KMA_HIP(hipMemcpy(d_props, props, n * sizeof(kma_proposal), hipMemcpyHostToDevice));
+  KMA_HIP(hipMemset(a.stats, 0, 32));
+  KMA_HIP(kma::launch_orf_extend(a, nullptr));
+  KMA_HIP(hipMemcpy(stats, a.stats, 32, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_left, a.left, n * 4, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_right, a.right, n * 4, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_status, a.status, n, hipMemcpyDeviceToHost));
   return KMA_OK;
 }
 

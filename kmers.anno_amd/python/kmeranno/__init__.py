@@ -23,6 +23,7 @@ E_IO = -7
 STATUS_NONE, STATUS_CALLED, STATUS_AMBIGUOUS, STATUS_BELOW_MIN = 0, 1, 2, 3
 F_END_EXCLUSIVE, F_MULTISET = 0x1, 0x2
 MAX_K = 12  # K <= 8: narrow tables (8-byte slots); 9..12: wide tables (16-byte slots)
+ORF_KEPT, ORF_REJECTED, ORF_WEAK, ORF_SMALL = 0, 1, 2, 3  # extend_proposals' status
 
 # Every symbol include/kmeranno.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -41,6 +42,7 @@ EXPORTS = (
     "kma_option_set", "kma_option_get", "kma_workspace_option_set",
     "kma_packed_bytes", "kma_pack_residues", "kma_annotate_packed_device",
     "kma_table_create_from_tsv", "kma_free",
+    "kma_orf_index_create", "kma_orf_index_destroy", "kma_extend_proposals",
 )
 
 # Tuning options (include/kmeranno.h "options"): library-wide defaults read per call.
@@ -160,6 +162,9 @@ def load(path: str | None = None):
                                         _int, _vp, _vp, _vp]
         L.kma_propose_pegs.argtypes = [_vp, _u64, _u32p, _u32, _int, C.c_double, C.c_double,
                                        C.c_double, _int, _vp, _u64, C.POINTER(_u64), _u64p]
+        L.kma_orf_index_create.argtypes = [_vp, _vp, _u32, _int, _int, C.POINTER(_vp)]
+        L.kma_orf_index_destroy.argtypes = [_vp]
+        L.kma_extend_proposals.argtypes = [_vp, _vp, _u64, C.c_double, _int, _vp, _vp, _vp, _vp]
         L.kma_contig_window_count.restype = _u64
         L.kma_contig_window_count.argtypes = [_u64p, _u32, _int]
         L.kma_option_set.argtypes = [_int, C.c_int64]
@@ -651,6 +656,60 @@ def propose_pegs(hits: np.ndarray, peg_len, k: int = 8, min_strength: float = 0.
             continue
         _check(rc)
         return out[:n.value], stats
+
+
+class OrfIndex:
+    """One genome's ORF index on one GPU (kma_orf_index_create): per (contig, strand, frame) the
+    next in-frame stop and the farthest start since the previous stop, built once per new genome
+    and read by extend_proposals for every close genome. dna / offsets as pack_strings gives
+    them; genetic_code 1, 4 or 11."""
+
+    def __init__(self, dna, offsets, genetic_code: int = 11, device: int = 0):
+        dna = np.ascontiguousarray(dna, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        self._h = None
+        h = _vp()
+        _check(load().kma_orf_index_create(dna.ctypes.data if len(dna) else None,
+                                           offsets.ctypes.data, len(offsets) - 1, genetic_code,
+                                           device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h:
+            load().kma_orf_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def extend_proposals(index: OrfIndex, proposals: np.ndarray, min_strength: float,
+                     min_evidence: int):
+    """PegProposalList.propose's first half on the GPU (kma_extend_proposals): every proposal
+    (PROPOSAL_DTYPE, as propose_pegs returns them) extended to its ORF and filtered. min_strength
+    is the DNA strength (minStrength / 3). Returns (left, right, status, stats[4] = made,
+    rejected, weak, small), entry i for proposal i; left = right = 0 where status is
+    ORF_REJECTED."""
+    if index._h is None:
+        raise KmerAnnoError(E_INVALID, "the ORF index is closed")
+    proposals = np.ascontiguousarray(proposals, PROPOSAL_DTYPE)
+    n = len(proposals)
+    left, right = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    status = np.zeros(n, np.uint8)
+    stats = np.zeros(4, np.uint64)
+    _check(load().kma_extend_proposals(index._h, proposals.ctypes.data if n else None, n,
+                                       min_strength, min_evidence, left.ctypes.data,
+                                       right.ctypes.data, status.ctypes.data, stats.ctypes.data))
+    return left, right, status, stats
 
 
 def hash_annotate(genome_residues, genome_offsets, proto_residues, proto_offsets, k: int = 8,

@@ -25,6 +25,9 @@ available). Restated choices, documented:
     in-order iteration are Java's for the same insertion order. merge() moves the kept
     proposal's begin in place (Location.setBegin), as in Java. oracle/proposal_list.py is the
     independent restatement the tests compare with.
+The extension and the strength / evidence filters also run on the GPU (kmeranno.OrfIndex,
+kmeranno.extend_proposals; csrc/kma_orf.hip restates extend a third time, include/kmeranno.h):
+annotate_proposals(extended=...) takes their arrays and keeps only the TreeSet here.
 """
 from __future__ import annotations
 
@@ -33,6 +36,7 @@ from dataclasses import dataclass
 _STOPS = {11: {"TAA", "TAG", "TGA"}, 1: {"TAA", "TAG", "TGA"}, 4: {"TAA", "TAG"}}
 _STARTS = {"ATG", "GTG", "TTG"}
 _COMP = str.maketrans("ACGTacgt", "TGCAtgca")
+_ORF_REJECTED, _ORF_WEAK, _ORF_SMALL = 1, 2, 3  # kmeranno.ORF_* (include/kmeranno.h)
 
 
 def _revcomp(s: str) -> str:
@@ -257,19 +261,37 @@ class PegProposalList:
         self.made = self.rejected = self.weak = self.small = self.merged = 0
         self._set = _TreeSet(lambda a, b: a.compare_to(b))
 
-    def propose(self, loc: Location, function: str, evidence: int) -> PegProposal | None:
+    def propose(self, loc: Location, function: str, evidence: int,
+                extended=None) -> PegProposal | None:
+        """extended = (left, right, status) of kmeranno.extend_proposals for this proposal: the
+        ORF and the rejected / weak / small decision come from the GPU (extend is not called);
+        None: both are computed here."""
         self.made += 1
-        real = extend(self.contigs[loc.contig], loc, self.gcode)
-        if real is None:
-            self.rejected += 1
-            return None
-        new = PegProposal(real, function, evidence)
-        if new.strength < self.min_strength:
-            self.weak += 1
-            return None
-        if evidence < self.min_evidence:
-            self.small += 1
-            return None
+        if extended is not None:
+            left, right, status = extended
+            if status == _ORF_REJECTED:
+                self.rejected += 1
+                return None
+            if status == _ORF_WEAK:
+                self.weak += 1
+                return None
+            if status == _ORF_SMALL:
+                self.small += 1
+                return None
+            new = PegProposal(Location(loc.contig, loc.strand, left, right, loc.contig_id),
+                              function, evidence)
+        else:
+            real = extend(self.contigs[loc.contig], loc, self.gcode)
+            if real is None:
+                self.rejected += 1
+                return None
+            new = PegProposal(real, function, evidence)
+            if new.strength < self.min_strength:
+                self.weak += 1
+                return None
+            if evidence < self.min_evidence:
+                self.small += 1
+                return None
         added, old = self._set.add(new)
         if added:
             return new
@@ -288,20 +310,28 @@ class PegProposalList:
 
 def annotate_proposals(proposals, functions: list[str], contigs: list[str], genome_id: str,
                        contig_ids: list[str], min_strength: float = 0.5, min_evidence: int = 10,
-                       gcode: int = 11):
+                       gcode: int = 11, extended=None):
     """KmerProcessor.annotateGenome's tail (:250-284): the sweep's proposals (PROPOSAL_DTYPE, in
     list order; peg index -> functions[peg]) through PegProposalList with the DNA strength
     min_strength / 3 (:170), then makeFeature (:295-312): [(fid, function, Location, evidence,
     strength)] in the list's order. contig_ids: the genome's contig ids, in contig-index order
     (required: PegProposal.compareTo orders by Location.getContigId, so the TreeSet's order and
-    the fig|...peg.N numbering depend on them)."""
+    the fig|...peg.N numbering depend on them). extended = (left, right, status) arrays of
+    kmeranno.extend_proposals for these proposals (an OrfIndex of this genome, the same
+    min_strength / 3, min_evidence and genetic code): the ORFs and the rejected / weak / small
+    filters are taken from them and extend is not called; the TreeSet insert, betterThan / merge
+    and the counters run as without them."""
     ids = list(contig_ids)
     if len(ids) != len(contigs):
         raise ValueError(f"{len(ids)} contig ids for {len(contigs)} contigs")
+    if extended is not None and any(len(x) != len(proposals) for x in extended):
+        raise ValueError("extended arrays and proposals differ in length")
     plist = PegProposalList(contigs, min_strength / 3, min_evidence, gcode)
-    for p in proposals:
+    for i, p in enumerate(proposals):
         c = int(p["contig"])
         loc = Location(c, chr(p["strand"]), int(p["left"]), int(p["right"]), ids[c])
-        plist.propose(loc, functions[int(p["peg"])], int(p["evidence"]))
+        ext = None if extended is None else (int(extended[0][i]), int(extended[1][i]),
+                                             int(extended[2][i]))
+        plist.propose(loc, functions[int(p["peg"])], int(p["evidence"]), ext)
     return [(f"fig|{genome_id}.peg.{i}", p.function, p.loc, p.evidence, p.strength)
             for i, p in enumerate(plist, start=1)], plist
