@@ -508,6 +508,45 @@ int kma_extend_proposals(const kma_orf_index* idx, const kma_proposal* props, ui
                          double min_strength, int min_evidence, int32_t* out_left,
                          int32_t* out_right, uint8_t* out_status, uint64_t* stats);
 
+/* ---- protein translation of locations (added under ABI 7) -------------------------------------
+ * KmerProcessor.makeFeature (anno/KmerProcessor.java:295-312) gives every kept proposal its
+ * protein: dna = genome.getDna(loc), prot = xlator.pegTranslate(dna, 1, dna.length() - 3).
+ * Genome.getDna and DnaTranslator.pegTranslate are external (org.theseed:shared); restated, as
+ * in kmeranno/projector.py peg_translate (the two must agree):
+ *
+ * A location (contig, strand, left, right) has 1-based inclusive forward edges and len = right
+ * - left + 1 bases. It yields len / 3 residues, or with KMA_TR_PEG max(0, len / 3 - 1): the
+ * last whole codon (the stop) is dropped. Residue j translates forward bases left + 3j, left +
+ * 3j + 1, left + 3j + 2 on '+', and right - 3j, right - 3j - 1, right - 3j - 2, each
+ * complemented, on '-'. Bases are case-insensitive ACGT; U reads as T (its complement is A); any
+ * other byte, bytes >= 128 included, makes its codon 'X' (as kma_annotate_contigs reads them).
+ * With KMA_TR_PEG residue 0 of a location is 'M' when its codon is ATG, GTG or TTG (the start
+ * set of the ORF index, under every genetic code); no other residue is changed. The rule is
+ * pinned by the stored translations of small.gto's pegs.
+ *
+ * kma_translate_locations: host buffers, synchronous, stateless; the DNA (contig c = dna[
+ * offsets[c] .. offsets[c + 1])) is uploaded to `device` per call. out_offsets[0 .. n_loc]
+ * (u64) are filled first: location i's residues are out_residues[out_offsets[i] ..
+ * out_offsets[i + 1]), ASCII, the layout kma_annotate_proteins takes. out_offsets[n_loc] > cap:
+ * KMA_E_CAPACITY with out_offsets filled (the need is readable) and no device touched; n_loc ==
+ * 0 or no residue at all: KMA_OK, offsets filled, no device touched. genetic_code: every NCBI
+ * table the library knows (1-6, 9-14, 16, 21-25); any other is KMA_E_INVALID. KMA_E_INVALID,
+ * naming the location's index: contig >= n_contig, a strand other than '+' / '-', left < 1,
+ * right > the contig's length, right < left - 1 (right == left - 1 is a legal empty location);
+ * also decreasing offsets, 2^31 bases or more, unknown flag bits, null arguments.              */
+typedef struct kma_location {
+  uint32_t contig;
+  int32_t left;
+  int32_t right;
+  uint8_t strand; /* '+' or '-' */
+  uint8_t pad[3];
+} kma_location;
+#define KMA_TR_PEG 1 /* pegTranslate(dna, 1, len - 3): last codon dropped, start codon -> 'M' */
+int kma_translate_locations(const uint8_t* dna, const uint64_t* offsets, uint32_t n_contig,
+                            int genetic_code, int device, const kma_location* locs,
+                            uint64_t n_loc, int flags, uint8_t* out_residues, uint64_t cap,
+                            uint64_t* out_offsets);
+
 /* ---- hash annotator scoring (HashAnnotationProcessor.java:221-328) ---------------------------
  * A genome's distinct protein sequences (the caller keys features by MD5, as GenomeProteinKmers
  * does; proteins holding '*' are left out, :239-241) against the prototypes of the role

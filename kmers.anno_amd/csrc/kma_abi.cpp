@@ -33,6 +33,7 @@
 #include "kma_internal.h"
 #include "kma_orf.h"
 #include "kma_pack.h"
+#include "kma_translate.h"
 #include "kma_tsv.h"
 
 namespace {
@@ -2831,6 +2832,108 @@ int kma_extend_proposals(const kma_orf_index* idx, const kma_proposal* props, ui
   KMA_HIP(hipMemcpy(out_status, a.status, n, hipMemcpyDeviceToHost));
   return KMA_OK;
 }
+
+}  // extern "C"
+
+// ---- protein translation of locations (kma_translate.hip) --------------------------------------
+namespace {
+thread_local double g_translate_kernel_ms = 0.0;  // the last call's kernel (kma_debug_translate_ms)
+}
+
+extern "C" {
+
+int kma_translate_locations(const uint8_t* dna, const uint64_t* offsets, uint32_t n_contig,
+                            int genetic_code, int device, const kma_location* locs,
+                            uint64_t n_loc, int flags, uint8_t* out_residues, uint64_t cap,
+                            uint64_t* out_offsets) {
+  g_translate_kernel_ms = 0.0;
+  if (!offsets || !out_offsets || (n_loc && !locs)) return fail(KMA_E_INVALID, "null argument");
+  if (flags & ~KMA_TR_PEG) return fail(KMA_E_INVALID, "unknown flag bits 0x%x", flags & ~KMA_TR_PEG);
+  const char* code = ncbi_code(genetic_code);
+  if (!code) return fail(KMA_E_INVALID, "genetic code %d is not a known NCBI table", genetic_code);
+  std::vector<uint64_t> off(n_contig + 1ull);
+  for (uint32_t c = 0; c < n_contig; ++c) {
+    if (offsets[c + 1] < offsets[c]) return fail(KMA_E_INVALID, "offsets decrease at %u", c);
+    if (offsets[c + 1] - offsets[0] >= (1ull << 31))
+      return fail(KMA_E_INVALID, "2^31 bases or more");
+    off[c + 1] = offsets[c + 1] - offsets[0];
+  }
+  const int64_t drop = flags & KMA_TR_PEG ? 1 : 0;
+  out_offsets[0] = 0;
+  for (uint64_t i = 0; i < n_loc; ++i) {
+    const kma_location& l = locs[i];
+    const unsigned long long ii = (unsigned long long)i;
+    if (l.contig >= n_contig)
+      return fail(KMA_E_INVALID, "location %llu: contig %u >= %u", ii, l.contig, n_contig);
+    if (l.strand != '+' && l.strand != '-')
+      return fail(KMA_E_INVALID, "location %llu: strand must be '+' or '-'", ii);
+    const int64_t n = (int64_t)(off[l.contig + 1] - off[l.contig]);
+    if (l.left < 1) return fail(KMA_E_INVALID, "location %llu: left %d < 1", ii, l.left);
+    if (l.right > n)
+      return fail(KMA_E_INVALID, "location %llu: right %d past the contig's %lld bases", ii,
+                  l.right, (long long)n);
+    if ((int64_t)l.right < (int64_t)l.left - 1)
+      return fail(KMA_E_INVALID, "location %llu: right %d < left %d - 1", ii, l.right, l.left);
+    const int64_t codons = ((int64_t)l.right - l.left + 1) / 3 - drop;
+    out_offsets[i + 1] = out_offsets[i] + (uint64_t)(codons > 0 ? codons : 0);
+  }
+  const uint64_t total = out_offsets[n_loc];
+  if (total > cap)
+    return fail(KMA_E_CAPACITY, "%llu residues, capacity %llu", (unsigned long long)total,
+                (unsigned long long)cap);
+  if (total == 0) return KMA_OK;
+  if (!dna || !out_residues) return fail(KMA_E_INVALID, "null argument");
+  DeviceScope ds(device);
+  if (ds.err != hipSuccess) return fail(KMA_E_DEVICE, "hipSetDevice(%d): %s", device,
+                                        hipGetErrorString(ds.err));
+  DevBufs b;
+  uint8_t *d_dna, *d_code, *d_out;
+  uint64_t *d_off, *d_ooff;
+  kma_location* d_locs;
+  const uint64_t bases = off[n_contig];
+  KMA_HIP(b.alloc(&d_dna, bases));
+  KMA_HIP(b.alloc(&d_off, (n_contig + 1ull) * 8));
+  KMA_HIP(b.alloc(&d_locs, n_loc * sizeof(kma_location)));
+  KMA_HIP(b.alloc(&d_ooff, (n_loc + 1) * 8));
+  KMA_HIP(b.alloc(&d_code, 64));
+  KMA_HIP(b.alloc(&d_out, total));
+  KMA_HIP(hipMemcpy(d_dna, dna + offsets[0], bases, hipMemcpyHostToDevice));
+  KMA_HIP(hipMemcpy(d_off, off.data(), (n_contig + 1ull) * 8, hipMemcpyHostToDevice));
+  KMA_HIP(hipMemcpy(d_locs, locs, n_loc * sizeof(kma_location), hipMemcpyHostToDevice));
+  KMA_HIP(hipMemcpy(d_ooff, out_offsets, (n_loc + 1) * 8, hipMemcpyHostToDevice));
+  KMA_HIP(hipMemcpy(d_code, code, 64, hipMemcpyHostToDevice));
+  kma::TranslateArgs a{};
+  a.dna = d_dna;
+  a.offsets = d_off;
+  a.locs = d_locs;
+  a.out_off = d_ooff;
+  a.n_loc = n_loc;
+  a.total = total;
+  a.code = d_code;
+  a.peg = (uint32_t)(flags & KMA_TR_PEG);
+  a.out = d_out;
+  struct Events {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  KMA_HIP(hipEventCreate(&ev.e[0]));
+  KMA_HIP(hipEventCreate(&ev.e[1]));
+  KMA_HIP(hipEventRecord(ev.e[0], nullptr));
+  KMA_HIP(kma::launch_translate(a, nullptr));
+  KMA_HIP(hipEventRecord(ev.e[1], nullptr));
+  KMA_HIP(hipMemcpy(out_residues, d_out, total, hipMemcpyDeviceToHost));
+  float ms = 0.f;
+  KMA_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  g_translate_kernel_ms = ms;
+  return KMA_OK;
+}
+
+// Not in kmeranno.h: measurement hook. hipEvent time of the kernel of this thread's last
+// kma_translate_locations call (0 when it launched none).
+double kma_debug_translate_ms(void) { return g_translate_kernel_ms; }
 
 }  // extern "C"
 

@@ -24,6 +24,7 @@ STATUS_NONE, STATUS_CALLED, STATUS_AMBIGUOUS, STATUS_BELOW_MIN = 0, 1, 2, 3
 F_END_EXCLUSIVE, F_MULTISET = 0x1, 0x2
 MAX_K = 12  # K <= 8: narrow tables (8-byte slots); 9..12: wide tables (16-byte slots)
 ORF_KEPT, ORF_REJECTED, ORF_WEAK, ORF_SMALL = 0, 1, 2, 3  # extend_proposals' status
+TR_PEG = 1  # translate_locations' flag: pegTranslate (last codon dropped, start codon -> 'M')
 
 # Every symbol include/kmeranno.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -43,6 +44,7 @@ EXPORTS = (
     "kma_packed_bytes", "kma_pack_residues", "kma_annotate_packed_device",
     "kma_table_create_from_tsv", "kma_free",
     "kma_orf_index_create", "kma_orf_index_destroy", "kma_extend_proposals",
+    "kma_translate_locations",
 )
 
 # Tuning options (include/kmeranno.h "options"): library-wide defaults read per call.
@@ -85,6 +87,8 @@ HIT_DTYPE = np.dtype([("contig", "<u4"), ("left", "<i4"), ("fid", "<u4"), ("stra
 PROPOSAL_DTYPE = np.dtype([("peg", "<u4"), ("contig", "<u4"), ("left", "<i4"), ("right", "<i4"),
                            ("evidence", "<u4"), ("strand", "u1"), ("frame", "u1"),
                            ("pad", "<u2")])
+LOCATION_DTYPE = np.dtype([("contig", "<u4"), ("left", "<i4"), ("right", "<i4"),
+                           ("strand", "u1"), ("pad", "u1", (3,))])
 
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C")
@@ -165,6 +169,10 @@ def load(path: str | None = None):
         L.kma_orf_index_create.argtypes = [_vp, _vp, _u32, _int, _int, C.POINTER(_vp)]
         L.kma_orf_index_destroy.argtypes = [_vp]
         L.kma_extend_proposals.argtypes = [_vp, _vp, _u64, C.c_double, _int, _vp, _vp, _vp, _vp]
+        L.kma_translate_locations.argtypes = [_vp, _vp, _u32, _int, _int, _vp, _u64, _int, _vp,
+                                              _u64, _vp]
+        L.kma_debug_translate_ms.restype = C.c_double
+        L.kma_debug_translate_ms.argtypes = []
         L.kma_contig_window_count.restype = _u64
         L.kma_contig_window_count.argtypes = [_u64p, _u32, _int]
         L.kma_option_set.argtypes = [_int, C.c_int64]
@@ -710,6 +718,48 @@ def extend_proposals(index: OrfIndex, proposals: np.ndarray, min_strength: float
                                        min_strength, min_evidence, left.ctypes.data,
                                        right.ctypes.data, status.ctypes.data, stats.ctypes.data))
     return left, right, status, stats
+
+
+def make_locations(rows) -> np.ndarray:
+    """rows of (contig index, strand '+' / '-', left, right) -> LOCATION_DTYPE."""
+    rows = list(rows)
+    locs = np.zeros(len(rows), LOCATION_DTYPE)
+    if rows:
+        locs["contig"] = [r[0] for r in rows]
+        locs["strand"] = [ord(r[1]) for r in rows]
+        locs["left"] = [r[2] for r in rows]
+        locs["right"] = [r[3] for r in rows]
+    return locs
+
+
+def translate_locations(dna, offsets, locs, genetic_code: int = 11, peg: bool = False,
+                        device: int = 0):
+    """kma_translate_locations: the proteins of locations (LOCATION_DTYPE; 1-based inclusive
+    forward edges, either strand) of a genome (dna / offsets as pack_strings gives them) on the
+    GPU. peg: KmerProcessor.makeFeature's pegTranslate (the last codon dropped, a start codon
+    first gives 'M'). Returns (residues u8 padded by 32 bytes, offsets u64), the layout
+    annotate_proteins takes. The output is sized here by the library's own length rule (invalid
+    locations are the library's to refuse)."""
+    dna = np.ascontiguousarray(dna, np.uint8)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    locs = np.ascontiguousarray(locs, LOCATION_DTYPE)
+    n = len(locs)
+    codons = (locs["right"].astype(np.int64) - locs["left"] + 1) // 3 - (1 if peg else 0)
+    total = int(np.maximum(codons, 0).sum())
+    out = np.zeros(total + 32, np.uint8)
+    out_off = np.zeros(n + 1, np.uint64)
+    _check(load().kma_translate_locations(dna.ctypes.data if len(dna) else None,
+                                          offsets.ctypes.data, len(offsets) - 1, genetic_code,
+                                          device, locs.ctypes.data if n else None, n,
+                                          TR_PEG if peg else 0, out.ctypes.data, total,
+                                          out_off.ctypes.data))
+    return out, out_off
+
+
+def translate_kernel_ms() -> float:
+    """hipEvent time of the kernel of this thread's last translate_locations call (measurement
+    hook, not in kmeranno.h)."""
+    return float(load().kma_debug_translate_ms())
 
 
 def hash_annotate(genome_residues, genome_offsets, proto_residues, proto_offsets, k: int = 8,

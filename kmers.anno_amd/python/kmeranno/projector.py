@@ -28,6 +28,12 @@ available). Restated choices, documented:
 The extension and the strength / evidence filters also run on the GPU (kmeranno.OrfIndex,
 kmeranno.extend_proposals; csrc/kma_orf.hip restates extend a third time, include/kmeranno.h):
 annotate_proposals(extended=...) takes their arrays and keeps only the TreeSet here.
+makeFeature's protein (Genome.getDna + DnaTranslator.pegTranslate, both EXTERNAL) is restated as
+peg_translate below and computed on the GPU by kmeranno.translate_locations
+(csrc/kma_translate.hip); unlike extend, its rule is pinned by the stored translations of the
+reference's small.gto (tests/test_translate_host.py). make_features builds the GTO feature
+records on top of it, and project_genome runs annotateGenome (:166-287) from a new genome and
+its close genomes through to those features (kmeranno.project is the command).
 """
 from __future__ import annotations
 
@@ -335,3 +341,143 @@ def annotate_proposals(proposals, functions: list[str], contigs: list[str], geno
         plist.propose(loc, functions[int(p["peg"])], int(p["evidence"]), ext)
     return [(f"fig|{genome_id}.peg.{i}", p.function, p.loc, p.evidence, p.strength)
             for i, p in enumerate(plist, start=1)], plist
+
+
+# ---- makeFeature's protein (KmerProcessor.java:303-306) -------------------------------------------
+# NCBI translation tables, codons in T, C, A, G order (the tables kma_translate_locations knows).
+_NCBI = {
+    1: "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+    2: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSS**VVVVAAAADDEEGGGG",
+    3: "FFLLSSSSYY**CCWWTTTTPPPPHHQQRRRRIIMMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+    4: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+    5: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSSSSVVVVAAAADDEEGGGG",
+    6: "FFLLSSSSYYQQCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+    9: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNNKSSSSVVVVAAAADDEEGGGG",
+    10: "FFLLSSSSYY**CCCWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+    12: "FFLLSSSSYY**CC*WLLLSPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+    13: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSSGGVVVVAAAADDEEGGGG",
+    14: "FFLLSSSSYYY*CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNNKSSSSVVVVAAAADDEEGGGG",
+    16: "FFLLSSSSYY*LCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+    21: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNNKSSSSVVVVAAAADDEEGGGG",
+    22: "FFLLSS*SYY*LCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+    23: "FF*LSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+    24: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSSKVVVVAAAADDEEGGGG",
+    25: "FFLLSSSSYY**CCGWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+}
+_NCBI[11] = _NCBI[1]
+_FOLD = str.maketrans("acgtuU", "ACGTTT")            # case-insensitive; U reads as T
+_FOLD_RC = str.maketrans("ACGTUacgtu", "TGCAATGCAA")  # the same, complemented (U -> A)
+_CODONS: dict = {}
+
+
+def _codon_table(gcode: int) -> dict:
+    tab = _CODONS.get(gcode)
+    if tab is None:
+        if gcode not in _NCBI:
+            raise ValueError(f"genetic code {gcode} is not a known NCBI table")
+        tab = _CODONS[gcode] = {a + b + c: _NCBI[gcode][16 * i + 4 * j + k]
+                                for i, a in enumerate("TCAG") for j, b in enumerate("TCAG")
+                                for k, c in enumerate("TCAG")}
+    return tab
+
+
+def peg_translate(dna: str, loc: Location, gcode: int = 11, peg: bool = True) -> str:
+    """Genome.getDna(loc) + DnaTranslator.pegTranslate(dna, 1, len - 3) restated (both external;
+    KmerProcessor.java:304-305); dna is the contig sequence. The location's bases in strand
+    order ('-': the reverse complement), translated codon by codon from its first base: bases
+    are case-insensitive ACGT, U reads as T, any other character makes its codon 'X'. peg: the
+    last whole codon (the stop) is dropped and the first residue is 'M' when the first codon is
+    ATG, GTG or TTG, whatever the genetic code; peg=False: every whole codon, no start rule.
+    The rule kma_translate_locations computes on the GPU (include/kmeranno.h); pinned by the
+    stored translations of small.gto's pegs."""
+    tab = _codon_table(gcode)
+    seq = dna[max(loc.left - 1, 0):max(loc.right, 0)]
+    seq = seq.translate(_FOLD) if loc.strand == "+" else seq.translate(_FOLD_RC)[::-1]
+    n = len(seq) // 3 - (1 if peg else 0)
+    if n <= 0:
+        return ""
+    prot = "".join([tab.get(seq[p:p + 3], "X") for p in range(0, 3 * n, 3)])
+    if peg and seq[:3] in _STARTS:
+        prot = "M" + prot[1:]
+    return prot
+
+
+def _java_4f(x: float) -> str:
+    """String.format("%2.4f", x): java.util.Formatter rounds the shortest decimal that names the
+    double HALF_UP (9/32 -> 0.2813, where C's printf gives 0.2812)."""
+    from decimal import ROUND_HALF_UP, Decimal
+    return str(Decimal(repr(float(x))).quantize(Decimal("0.0001"), rounding=ROUND_HALF_UP))
+
+
+def make_features(feats, contigs_dna, offsets, gcode: int, device: int = 0, timestamp=None):
+    """KmerProcessor.makeFeature (:295-312) for annotate_proposals' feature tuples (fid,
+    function, Location with its contig_id, evidence, strength): GTO feature dicts in the shape
+    of the reference's fixtures, each with its protein from one translate_locations(peg=True)
+    call over all of them (contigs_dna / offsets: the new genome as pack_strings gives it) and
+    the two annotations of :308-309 by "kmers.anno", stamped `timestamp` (None: now)."""
+    import time
+
+    import kmeranno
+    feats = list(feats)
+    locs = kmeranno.make_locations((f[2].contig, f[2].strand, f[2].left, f[2].right)
+                                   for f in feats)
+    res, off = kmeranno.translate_locations(contigs_dna, offsets, locs, gcode, peg=True,
+                                            device=device)
+    text = res.tobytes()
+    stamp = time.time() if timestamp is None else timestamp
+    out = []
+    for i, (fid, function, loc, evidence, strength) in enumerate(feats):
+        note = "Annotated with evidence %d and strength %s" % (evidence, _java_4f(strength))
+        out.append({
+            "id": fid, "type": "CDS", "function": function,
+            "location": [[loc.contig_id, str(loc.begin), loc.strand, loc.length]],
+            "protein_translation": text[int(off[i]):int(off[i + 1])].decode("ascii"),
+            "annotations": [[note, "kmers.anno", stamp, ""],
+                            ["Set function to " + function, "kmers.anno", stamp, ""]],
+        })
+    return out
+
+
+def project_genome(new_gto: dict, close_gtos, *, k: int = 8, strict: bool = False,
+                   min_strength: float = 0.5, max_fuzz: float = 1.5, min_fuzz: float = 0.8,
+                   min_evidence: int = 10, max_genomes: int = 10, device: int = 0,
+                   timestamp=None):
+    """KmerProcessor.annotateGenome (:166-287) with the defaults of :144-150: the pegs of the
+    first max_genomes close genomes (GTO dicts, in the given order; fetching them is the
+    caller's) projected onto the new genome, every stage but the TreeSet on the GPU. One ORF
+    index and one PegProposalList per new genome; per close genome the peg table, the join
+    (strict: KmerFactory.Strict), the proposal sweep and the ORF extension, proposed in the
+    sweep's order; then make_features. The genetic code is new_gto["genetic_code"]. Returns
+    (features, counters): the GTO feature dicts in the list's order and the counts logged at
+    :273 (made, merged, rejected, weak, small, kept)."""
+    import numpy as np
+
+    import kmeranno
+    gcode = int(new_gto.get("genetic_code", 11))
+    contigs = [c["dna"] for c in new_gto["contigs"]]
+    ids = [c["id"] for c in new_gto["contigs"]]
+    dna, doff = kmeranno.pack_strings(contigs)
+    plist = PegProposalList(contigs, min_strength / 3, min_evidence, gcode)
+    with kmeranno.OrfIndex(dna, doff, gcode, device) as index:
+        for close in list(close_gtos)[:max_genomes]:
+            pegs = [f for f in close["features"] if f.get("protein_translation")]
+            res, off = kmeranno.pack_strings([f["protein_translation"] for f in pegs])
+            table, _ = kmeranno.SignatureTable.from_pegs(res, off, k, device)
+            with table:
+                hits = kmeranno.connect_pegs(table, dna, doff, gcode, strict)
+            peg_len = np.diff(off).astype(np.uint32)
+            props, _ = kmeranno.propose_pegs(hits, peg_len, k, min_strength, max_fuzz, min_fuzz,
+                                             device)
+            left, right, status, _ = kmeranno.extend_proposals(index, props, min_strength / 3,
+                                                               min_evidence)
+            for i, p in enumerate(props):
+                c = int(p["contig"])
+                plist.propose(Location(c, chr(p["strand"]), int(p["left"]), int(p["right"]),
+                                       ids[c]),
+                              pegs[int(p["peg"])].get("function", ""), int(p["evidence"]),
+                              (int(left[i]), int(right[i]), int(status[i])))
+    feats = [(f"fig|{new_gto['id']}.peg.{i}", p.function, p.loc, p.evidence, p.strength)
+             for i, p in enumerate(plist, start=1)]
+    counters = {"made": plist.made, "merged": plist.merged, "rejected": plist.rejected,
+                "weak": plist.weak, "small": plist.small, "kept": len(plist)}
+    return make_features(feats, dna, doff, gcode, device, timestamp), counters
