@@ -184,8 +184,11 @@ int kma_device_count(int* out_n);
  *   KMA_OPT_PACKED_INPUT    protein calls [1]: residues are packed to 5 bits before the probe
  *                           and the probe reads the packed stream: host calls while staging
  *                           (the H2D moves 0.625 B per residue) under 1 and 2; device calls
- *                           with a pack kernel into the workspace under 2, and under 1 for
- *                           batches of >= 2^25 residues; 0 = the probe packs ASCII itself
+ *                           with a pack kernel into the workspace under 2 only; under 0 and
+ *                           1 the probe packs the ASCII residues itself, a block's span at a
+ *                           time in LDS, whatever the batch size (ABI 7 as first released
+ *                           packed device batches of >= 2^25 residues under 1; results are
+ *                           the same either way)
  *   KMA_OPT_HOST_THREADS    host calls: threads staging (copying / packing) the input, the
  *                           whole call's budget split over the replicas it fans out to [0: each
  *                           of n replicas min(16, cores / n), cores = the process's CPUs bounded
@@ -360,7 +363,8 @@ int kma_annotate_proteins(const kma_table* table, const uint8_t* residues,
  * d_tally (n_fid u32) is accumulated into, not cleared. Asynchronous on `stream`: one kernel
  * launch (annotate_kernel: each window probes the table where it stands, per-protein sets and
  * the vote in LDS), preceded by a pack kernel into the workspace under KMA_OPT_PACKED_INPUT
- * (default: batches of >= 2^25 residues).                                                      */
+ * = 2 only. (Of that padding annotate_kernel reads at most the aligned 8-byte word after the
+ * one that holds the last residue.)                                                            */
 int kma_annotate_proteins_device(const kma_table* table, kma_workspace* ws,
                                  const uint8_t* d_residues, const uint64_t* d_offsets,
                                  uint32_t n_seq, uint64_t n_residues, int min_hits,

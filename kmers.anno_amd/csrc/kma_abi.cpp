@@ -1459,20 +1459,20 @@ uint32_t defer_below(const kma_workspace* ws, uint64_t n_groups) {
   return n_groups > slots && n_groups <= 4 * slots ? 3u : 0u;
 }
 
-// How the protein kernel gets its residues: ASCII read directly; ASCII packed on the device
-// first (pack_kernel into the workspace, then the packed kernel: the device entry point's
-// default, KMA_OPT_PACKED_INPUT); a packed stream the caller staged (host entry, packed device
-// entry; stream residue `stream_first` = residue offsets[0]).
+// How the protein kernel gets its residues: ASCII, which each block packs into its LDS stage
+// as it goes (the device entry point's default); ASCII packed on the device first (pack_kernel
+// into the workspace, then the packed kernel: KMA_OPT_PACKED_INPUT = 2); a packed stream the
+// caller staged (host entry, packed device entry; stream residue `stream_first` = residue
+// offsets[0]).
 enum class Input { kAscii, kPackOnDevice, kStream };
 
-// Device calls pack first under KMA_OPT_PACKED_INPUT = 2, or = 1 (the default) for batches of
-// at least 2^25 residues: the pack kernel costs a launch (~8 us at c2's 3M residues, where the
-// ASCII probe is 3 us faster in total) and pays off only at scale (c4 2.80 vs 2.83 ms, c5 even:
-// profiles/r04/ab_r04c.jsonl). Host calls pack under 1 and 2 (the H2D is the bound there).
-constexpr uint64_t kPackMinResidues = 1ull << 25;
+// Device calls of every size run the staged ASCII probe alone under KMA_OPT_PACKED_INPUT = 0 and
+// 1 (the default): the pack pass read 1 B and wrote 0.625 B per residue for the probe to read
+// back, a launch and ~0.1 ms of c5's step on the fabric the probe is bound by.
+// 2 keeps the pack kernel + stream probe: the control arm of that measurement. Host calls pack
+// under 1 and 2 (the H2D is the bound there).
 bool pack_on_device(uint64_t n_residues) {
-  const int64_t v = opt(KMA_OPT_PACKED_INPUT);
-  return n_residues > 0 && (v == 2 || (v == 1 && n_residues >= kPackMinResidues));
+  return n_residues > 0 && opt(KMA_OPT_PACKED_INPUT) == 2;
 }
 
 // The workspace's packed stream for device calls that pack: allocated by

@@ -46,18 +46,13 @@ __device__ __forceinline__ uint64_t window_bytes(const uint8_t* __restrict__ res
   const uint64_t* src = reinterpret_cast<const uint64_t*>(res + (pos & ~7ull));
   return funnel(src[0], src[1], (uint32_t)(pos & 7) * 8u);
 }
-// The two aligned words of a window, combined later (win_bytes: a funnel shift) so that the
+// The two aligned words of a window, combined later (packed_key: a funnel shift) so that the
 // load is not consumed in the step that issues it. (One unaligned 8-byte load per window saves
 // 3 VGPRs and measured 1% slower at c5, profiles/r03t/.)
 struct WinWords {
   uint64_t lo, hi;
   uint32_t sh;
 };
-__device__ __forceinline__ WinWords window_words(const uint8_t* __restrict__ res, uint64_t pos) {
-  const uint64_t* src = reinterpret_cast<const uint64_t*>(res + (pos & ~7ull));
-  return WinWords{src[0], src[1], (uint32_t)(pos & 7) * 8u};
-}
-__device__ __forceinline__ uint64_t win_bytes(const WinWords& w) { return funnel(w.lo, w.hi, w.sh); }
 
 // Packed residue streams (kma_pack_residues, pack_residues_kernel): residue j of a call is the
 // 5-bit code at bits [5j, 5j + 5) of a big-endian bit stream (stream byte b holds bits
@@ -85,21 +80,22 @@ __device__ __forceinline__ uint64_t packed_key(const WinWords& w) {
   return (be << (w.sh & 7u)) >> (64 - 5 * K);
 }
 
-// 5-bit packing through the table's residue LUT (LDS); false if a byte is not encodable.
-template <int K>
-__device__ __forceinline__ bool pack_window(const uint8_t* lut, uint64_t bytes, uint64_t& key) {
-  uint32_t c[K];
+// Eight residues (byte j of `bytes` = residue j) through the table's residue LUT into their 40
+// stream bits, first residue most significant; a byte without a code leaves a zero group. The
+// one ASCII -> stream step of the device: the pack kernel and the staged probe both use it.
+__host__ __device__ __forceinline__ uint64_t pack8(const uint8_t* lut, uint64_t bytes) {
+  uint32_t c[8];
 #pragma unroll
-  for (int j = 0; j < K; ++j) c[j] = lut[(uint32_t)(bytes >> (8 * j)) & 0xFFu];
+  for (int j = 0; j < 8; ++j) c[j] = lut[(uint32_t)(bytes >> (8 * j)) & 0xFFu];
   uint64_t v = 0;
-  bool ok = true;
 #pragma unroll
-  for (int j = 0; j < K; ++j) {
-    ok = ok && c[j] != 0u;
-    v = (v << 5) | c[j];
-  }
-  key = v;
-  return ok;
+  for (int j = 0; j < 8; ++j) v = (v << 5) | c[j];
+  return v;
+}
+// The 40 bits of pack8 as stream bytes at `out` (any alignment).
+__host__ __device__ __forceinline__ void store40(uint8_t* out, uint64_t v) {
+#pragma unroll
+  for (int b = 0; b < 5; ++b) out[b] = (uint8_t)(v >> (32 - 8 * b));
 }
 
 // One lane's scan of a whole bucket (the rare chain walk): the bucket's slots are loaded 64

@@ -397,6 +397,20 @@ constexpr int kWavesPerBlock = 4;
 #define KMA_PROTEIN_OCC 7
 #endif
 constexpr int kProteinOcc = KMA_PROTEIN_OCC;
+// The ASCII kernel's stage: a block packs kStageRes + 7 residues of its span at a time (whole
+// 8-residue groups, 5 bytes each) into the tail of its LDS pool and reads its windows from
+// there, as the packed kernel reads them from the stream. A multiple of a probe step's windows,
+// so a step never straddles two stages; the tail is rounded to the pool's 16-byte zeroing unit,
+// which also covers the second aligned word of the last window's read.
+#ifndef KMA_STAGE_RES
+#define KMA_STAGE_RES 1024
+#endif
+constexpr int kStageRes = KMA_STAGE_RES;
+constexpr int kStageGroups = kStageRes / 8 + 1;
+constexpr int kStageEntries = (5 * kStageGroups + 15) / 16 * 4;  // u32 pool entries
+static_assert(kStageRes % (256 * kProbeWin) == 0, "a stage holds whole probe steps");
+static_assert(4 * kStageEntries >= 5 * kStageRes / 8 + 8, "the last window reads two aligned words");
+static_assert(kStageEntries < kSetPool / 2, "the stage leaves most of the pool to the sets");
 
 struct ProteinArgs {
   const uint64_t* slots;

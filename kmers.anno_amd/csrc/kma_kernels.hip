@@ -580,33 +580,74 @@ __device__ __forceinline__ const uint8_t* head_res(const ProteinArgs& a, const G
   pos0 = (uintptr_t)res0 & 7u;
   return res0 - pos0;
 }
-template <bool Packed>
-__device__ __forceinline__ WinWords load_win(const uint8_t* __restrict__ res, uint64_t pos) {
-  return Packed ? window_words_packed(res, pos) : window_words(res, pos);
-}
-// The group's first probe step's residue words (clamped to the batch, which is readable past
+// The group's first probe step's stream words (clamped to the batch, which is readable past
 // its end; windows past the span are masked in the loop).
-template <int U, bool Packed>
+template <int U>
 __device__ __forceinline__ void head_residues(const ProteinArgs& a, const GroupHead& h,
                                               uint32_t tw, WinWords (&ww)[U]) {
   uint64_t pos0;
-  const uint8_t* res = head_res<Packed>(a, h, pos0);
+  const uint8_t* res = head_res<true>(a, h, pos0);
   const uint64_t lim = a.n_residues - h.span_lo;
 #pragma unroll
   for (int j = 0; j < U; ++j) {
     const uint32_t x = j * 256u + tw;
-    ww[j] = load_win<Packed>(res, (x < lim ? x : 0u) + pos0);
+    ww[j] = window_words_packed(res, (x < lim ? x : 0u) + pos0);
+  }
+}
+
+// The ASCII kernel's stage (kma_internal.h): the block's thread t takes the 8-residue groups t,
+// t + 256, .. of the stage at span position xc (a multiple of kStageRes). Group g is the span's
+// residues [xc + 8 g, xc + 8 g + 8): the two aligned words around them, funnelled as a window's
+// bytes are (`res` and `sh` from head_res<false>). Only groups that start below `lim` (the
+// span's length, or what is left of the batch while the span is not known yet) are read, so
+// the last word read is the one the last window's own ASCII load would read; the others read
+// the span's first words and are stored as zero groups. The words wait in the lane's window
+// registers ww[i].lo / .hi, which are free between a step's keys and the next step's windows:
+// registers of their own spilled at 7 waves per SIMD.
+constexpr int kStagePerThread = (kStageGroups + 255) / 256;
+static_assert(kStagePerThread <= kProbeWin, "a lane's stage words wait in its window registers");
+__device__ __forceinline__ void stage_fetch(const uint8_t* __restrict__ res, uint32_t xc,
+                                            uint32_t lim, WinWords (&ww)[kProbeWin]) {
+  const uint64_t* words = reinterpret_cast<const uint64_t*>(res) + (xc >> 3);
+#pragma unroll
+  for (int i = 0; i < kStagePerThread; ++i) {
+    const uint32_t g = threadIdx.x + 256u * i;
+    const bool in = g < (uint32_t)kStageGroups && xc < lim && 8u * g < lim - xc;
+    const uint64_t* src = in ? words + g : reinterpret_cast<const uint64_t*>(res);
+    ww[i].lo = src[0];
+    ww[i].hi = src[1];
+  }
+}
+__device__ __forceinline__ void stage_store(uint8_t* stage, const uint8_t* lut, uint32_t sh,
+                                            uint32_t xc, uint32_t lim,
+                                            const WinWords (&ww)[kProbeWin]) {
+#pragma unroll
+  for (int i = 0; i < kStagePerThread; ++i) {
+    const uint32_t g = threadIdx.x + 256u * i;
+    if (g < (uint32_t)kStageGroups) {
+      const bool in = xc < lim && 8u * g < lim - xc;
+      store40(stage + 5u * g, in ? pack8(lut, funnel(ww[i].lo, ww[i].hi, sh)) : 0u);
+    }
   }
 }
 
 // The group h: proteins [p0, p0 + np) (np <= P), contiguous in the batch, whose first step's
-// residue words are in ww. pass 0 / 1: a block of the two-pass grid, which annotates its group
-// only if the group is long (pass 0) / short (pass 1: fewer than defer_below probe steps);
-// pass -1: always. sm.lut is being loaded (read after the first barrier).
+// stream words (Packed) or first stage's residue words (ASCII, stage_fetch) are in ww. pass
+// 0 / 1: a block of the two-pass grid, which annotates its group only if the group is long
+// (pass 0) / short (pass 1: fewer than defer_below probe steps); pass -1: always. sm.lut is
+// being loaded (read after the first barrier).
+//
+// ASCII residues (!Packed) are packed once per block into the stage, the last kStageEntries
+// entries of the pool (the sets take the rest), and every window then reads its key from
+// there exactly as the packed kernel reads it from the stream: two 8-byte LDS reads and a
+// funnel. The first stage is stored between the prologue's barriers; a span longer than
+// kStageRes stores the next one every kStageRes / (256 kProbeWin) steps between two block
+// barriers of its own (the loop's bounds are block-uniform).
 template <int K, int M, int P, bool Packed>
 __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem<P>& sm,
                                                const GroupHead& h, WinWords (&ww)[kProbeWin],
                                                const int pass = -1) {
+  constexpr uint32_t kPool = Packed ? kSetPool : kSetPool - kStageEntries;  // entries for sets
   constexpr int U = kProbeWin;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, part = t & 3;
   const bool multiset = (a.flags & KMA_F_MULTISET) != 0;
@@ -643,7 +684,7 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
       uint32_t sum = 0;
       for (int p = 0; p < P; ++p) sum += sm.pcap[p];
       uint32_t top = 0;
-      if (sum <= (uint32_t)kSetPool) {  // the usual case: every set in LDS, in protein order
+      if (sum <= kPool) {  // the usual case: every set in LDS, in protein order
         for (int p = 0; p < P; ++p) {
           sm.pset[p] = top;
           top += sm.pcap[p];
@@ -658,7 +699,7 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
             if (!(done >> p & 1u) && (best < 0 || sm.pcap[p] > sm.pcap[best])) best = p;
           done |= 1u << best;
           const uint32_t cap = sm.pcap[best];
-          const bool fits = top + cap <= (uint32_t)kSetPool;
+          const bool fits = top + cap <= kPool;
           sm.pset[best] = fits ? top : kGlobalSet;  // (a list: appended, never zeroed)
           top += fits ? cap : 0u;
         }
@@ -668,6 +709,10 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
   }
   __syncthreads();
   if (pass >= 0 && sm.skip) return;  // block-uniform
+  uint8_t* stage = reinterpret_cast<uint8_t*>(sm.pool + kPool);
+  const uint32_t stage_sh = (uint32_t)pos0 * 8u;
+  // the first stage: beside the zeroing of the sets below it, read after the third barrier
+  if (!Packed) stage_store(stage, sm.lut, stage_sh, 0u, a.n_residues - (uint32_t)span_lo, ww);
   const uint32_t used = sm.chain_q[0][0];
   uint32_t pb[P + 1], pe[P];
 #pragma unroll
@@ -684,7 +729,6 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
   const uint64_t* __restrict__ slots = a.slots;
   const uint32_t nb = a.n_buckets;
   const bool two_choice = a.two_choice != 0;
-  const uint8_t* lut = sm.lut;
   uint32_t* cq = sm.chain_q[wave];
   uint32_t cn = 0;  // wave-uniform queue length
   constexpr uint32_t stride = 256u * U;
@@ -747,14 +791,9 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
     for (int j = 0; j < U; ++j) {
       const uint32_t x = xs + j * 256u + tw;
       const uint32_t p = protein_at<P>(pb, x);
-      uint64_t key;
-      bool ok;
-      if (Packed) {  // (key 0: every residue without a code; it would match an empty slot)
-        key = packed_key<K>(ww[j]);
-        ok = key != 0 && x < span && window_at<P>(pe, x, p);
-      } else {
-        ok = pack_window<K>(lut, win_bytes(ww[j]), key) && x < span && window_at<P>(pe, x, p);
-      }
+      // (key 0: every residue without a code; it would match an empty slot)
+      const uint64_t key = packed_key<K>(ww[j]);
+      const bool ok = key != 0 && x < span && window_at<P>(pe, x, p);
       o.klo[j] = (uint32_t)key;
       o.khi[j] = (uint32_t)(key >> 32) << 24 | (ok ? 0u : 1u);  // bit 0: does not probe
       o.need[j] = filter_need<kSlotsPerBucket>(o.klo[j]);
@@ -783,7 +822,10 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
 #pragma unroll
     for (int j = 0; j < U; ++j) {
       const uint32_t x = xs + j * 256u + tw;
-      ww[j] = load_win<Packed>(res, (x < span ? x : 0u) + pos0);
+      if (Packed)
+        ww[j] = window_words_packed(res, (x < span ? x : 0u) + pos0);
+      else  // (x's stage is the one in LDS; a step past the span reads stale groups, masked)
+        ww[j] = window_words_packed(stage, x % (uint32_t)kStageRes);
     }
   };
   // Compare the quad's buckets, record hits, queue chain walks.
@@ -844,15 +886,30 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
   // flight, so a wave's only exposed latency per step is the bucket gather. (A two-stage
   // pipeline packing step i + 1 under step i's gather measured 6.51 vs 4.48 ms at c5,
   // profiles/r03_ab/r03h_steps.log.)
+  if (!Packed) load_residues(0u);
   for (uint32_t x0 = 0; x0 < span; x0 += stride) {
     Prep cur;
     prep(x0, cur);
+    // The next step opens a new stage: its residue words are requested ahead of the bucket
+    // loads and stored under them. Every wave has taken this step's windows from the old stage
+    // once it is past prep, hence the first barrier. (Stored after settle instead: c5 2.768 vs
+    // 2.751 ms)
+    const uint32_t xn = x0 + stride;
+    const bool restage = !Packed && xn % (uint32_t)kStageRes == 0u && xn < span;  // block-uniform
+    if (restage) stage_fetch(res, xn, span, ww);
     uint4 q[U][4][kBucketHalves];
     gather(cur, q);
     // next step's residues (issued after the bucket loads: waiting for those leaves these in
     // flight, vmcnt counts in order)
-    load_residues(x0 + stride);  // (past the span: clamped to its first word)
+    if (Packed) load_residues(xn);  // (past the span: clamped to its first word)
+    if (restage) {  // (under the bucket loads: its words arrive first, the barriers wait with them)
+      __syncthreads();
+      stage_store(stage, sm.lut, stage_sh, xn, span, ww);
+      __syncthreads();
+    }
     settle(x0, cur, q);
+    // (from the stage: an LDS round trip, not worth ten registers held across the buckets)
+    if (!Packed) load_residues(xn);
     if (x0 == 0) KMA_CLK(2);
   }
   KMA_CLK(3);
@@ -882,12 +939,11 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
 }
 
 // Occupancy: kProteinOcc waves per SIMD (its LDS and VGPR budget); the flat layout's variants
-// (a fallback for crowded tables: two full-key mixes per window) and the mod-sampling order's
-// ASCII variant (the LUT pack of a window beside the order's ranks; small device calls only,
-// larger ones pack first) need 6 to stay clear of scratch.
+// (a fallback for crowded tables: two full-key mixes per window) need 6 to stay clear of
+// scratch.
 template <int K, int M, bool Packed>
 constexpr int protein_occ() {
-  return (M == 0 && (Packed || K < 8)) || (!Packed && (M & kOrderMod)) ? 6 : kProteinOcc;
+  return M == 0 ? 6 : kProteinOcc;
 }
 template <int K, int M, int P, bool Packed>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(protein_occ<K, M, Packed>(), 8))) void annotate_kernel(
@@ -909,8 +965,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(protein_occ
   // (the two-pass grid keeps block order: its long-first order is what it is for)
   const uint32_t b = blockIdx.x - (second ? a.n_groups : 0u);
   head_offsets(a, a.defer_below ? b : xcd_group(b, a.n_groups), h);
-  head_residues<kProbeWin, Packed>(a, h, lane_window(t), ww);
-  if (!Packed) sm.lut[t] = lut_b;
+  if (Packed) {
+    head_residues<kProbeWin>(a, h, lane_window(t), ww);
+  } else {  // the first stage's residue words (clamped to the batch: the span is not known yet)
+    uint64_t pos0;
+    const uint8_t* res = head_res<false>(a, h, pos0);
+    stage_fetch(res, 0u, a.n_residues - (uint32_t)h.span_lo, ww);  // (span_lo <= n_residues)
+    sm.lut[t] = lut_b;
+  }
   annotate_block<K, M, P, Packed>(a, sm, h, ww, a.defer_below ? (second ? 1 : 0) : -1);
   KMA_CLK(5);
   KMA_CLK_HW();
@@ -1517,18 +1579,19 @@ __global__ __launch_bounds__(256) void contigs_emit_kernel(ContigArgs a, uint32_
 // funnel shift per word; the last, partial group by bytes. Reads 1 B and writes 0.625 B per
 // residue: ~0.1 ms for c5's 310M residues.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void pack64(const uint8_t (&lut)[256], const uint8_t (&b)[64],
+// (x[k]: residues 8 k .. 8 k + 7 of the group, byte j = residue j; 40 stream bits each, pack8)
+__device__ __forceinline__ void pack64(const uint8_t (&lut)[256], const uint64_t (&x)[8],
                                        uint64_t* __restrict__ out) {
   uint64_t w[5] = {0, 0, 0, 0, 0};
 #pragma unroll
-  for (int i = 0; i < 64; ++i) {
-    const uint64_t c = lut[b[i]];
-    const int k = (5 * i) >> 6, o = (5 * i) & 63;  // MSB-first bit o of stream word k
-    if (o <= 59) {
-      w[k] |= c << (59 - o);
+  for (int i = 0; i < 8; ++i) {
+    const uint64_t c = pack8(lut, x[i]);
+    const int k = (40 * i) >> 6, o = (40 * i) & 63;  // MSB-first bit o of stream word k
+    if (o <= 24) {
+      w[k] |= c << (24 - o);
     } else {
-      w[k] |= c >> (o - 59);
-      w[k + 1] |= c << (123 - o);
+      w[k] |= c >> (o - 24);
+      w[k + 1] |= c << (88 - o);
     }
   }
 #pragma unroll
@@ -1547,22 +1610,25 @@ __global__ __launch_bounds__(256) void pack_residues_kernel(const uint8_t* __res
   const uint64_t* aligned = reinterpret_cast<const uint64_t*>(base - mis);
   const uint64_t groups = (n + 63) / 64;
   for (uint64_t g = blockIdx.x * 256ull + threadIdx.x; g < groups; g += gridDim.x * 256ull) {
-    uint8_t b[64];
+    uint64_t x[8];
     if (64 * g + 64 <= n) {  // whole group: 9 aligned words (the batch is readable past its end)
       uint64_t v[9];
 #pragma unroll
       for (int k = 0; k < 9; ++k) v[k] = aligned[8 * g + k];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const uint64_t x = funnel(v[k], v[k + 1], mis * 8u);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) b[8 * k + j] = (uint8_t)(x >> (8 * j));
-      }
+      for (int k = 0; k < 8; ++k) x[k] = funnel(v[k], v[k + 1], mis * 8u);
     } else {
 #pragma unroll
-      for (int i = 0; i < 64; ++i) b[i] = 64 * g + i < n ? base[64 * g + i] : 0u;
+      for (int k = 0; k < 8; ++k) {
+        x[k] = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const uint64_t i = 64 * g + 8 * k + j;
+          x[k] |= (uint64_t)(i < n ? base[i] : 0u) << (8 * j);
+        }
+      }
     }
-    pack64(lut, b, out + 5 * g);
+    pack64(lut, x, out + 5 * g);
   }
   if (blockIdx.x == 0 && threadIdx.x < 2) out[5 * groups + threadIdx.x] = 0;  // read padding
 }
