@@ -273,6 +273,27 @@ def _dump_rows(k, seed, n=20_000):
     return keys, fids, want
 
 
+def decode_slots(raw, k):
+    """The (key, fid) of every used slot of a slot array copied back as u64 words, decoded as
+    include/kmeranno.h documents the slots: narrow (K <= 8) key bits 0..31 in the low dword and
+    key bits 32..39 << 24 | filter bits << 22 | fid in the high one; wide .x .y the key, .z filter
+    bits << 22 | fid, .w 0. A slot is used when its low key dword is not 0."""
+    if k > 8:
+        q = raw.view(np.uint32).reshape(-1, 4)  # .x .y .z .w
+        assert (q[:, 3] == 0).all()
+        used = q[:, 0] != 0
+        got_keys = (q[used, 1].astype(np.uint64) << np.uint64(32)) | q[used, 0]
+        got_fids = q[used, 2] & np.uint32(FID_MASK)
+        assert (q[used, 2] >> np.uint32(FID_BITS + 2) == 0).all()  # fid and two filter bits only
+    else:
+        lo = (raw & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+        hi = (raw >> np.uint64(32)).astype(np.uint32)
+        used = lo != 0
+        got_keys = ((hi[used] >> np.uint32(24)).astype(np.uint64) << np.uint64(32)) | lo[used]
+        got_fids = hi[used] & np.uint32(FID_MASK)
+    return got_keys, got_fids
+
+
 @pytest.mark.parametrize("k,layout_name", [(8, "two-choice"), (8, "chained"), (8, "flat"),
                                            (10, "chained")])
 def test_build_device_slot_dump_equals_rows(kma, k, layout_name):
@@ -300,21 +321,8 @@ def test_build_device_slot_dump_equals_rows(kma, k, layout_name):
     torch.cuda.synchronize()
     st = status.cpu().numpy()
     assert st[0] == 0 and st[1] == len(want) and st[3] > 0, st.tolist()
-    raw = slots.cpu().numpy().view(np.uint64)
-    if k > 8:
-        q = raw.view(np.uint32).reshape(-1, 4)  # .x .y .z .w
-        assert (q[:, 3] == 0).all()
-        used = q[:, 0] != 0
-        got_keys = (q[used, 1].astype(np.uint64) << np.uint64(32)) | q[used, 0]
-        got_fids = q[used, 2] & np.uint32(FID_MASK)
-        assert (q[used, 2] >> np.uint32(FID_BITS + 2) == 0).all()  # fid and two filter bits only
-    else:
-        lo = (raw & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-        hi = (raw >> np.uint64(32)).astype(np.uint32)
-        used = lo != 0
-        got_keys = ((hi[used] >> np.uint32(24)).astype(np.uint64) << np.uint64(32)) | lo[used]
-        got_fids = hi[used] & np.uint32(FID_MASK)
-    assert int(used.sum()) == len(want)
+    got_keys, got_fids = decode_slots(slots.cpu().numpy().view(np.uint64), k)
+    assert len(got_keys) == len(want)
     got = dict(zip(got_keys.tolist(), got_fids.tolist()))
     assert len(got) == len(want)  # no key twice
     assert got == want
