@@ -342,8 +342,17 @@ __global__ __launch_bounds__(256) void build_two_choice_filter_kernel(uint64_t* 
 // and the set of distinct keys hit (ProteinKmers is a set: a kmer occurring twice counts
 // once; a key's slot id is its identity in the table). After one barrier the vote is read off
 // the record, order-free: no hit -> NONE (roleId == null); smallest != largest -> AMBIGUOUS
-// (badPeg); else the role with count = |set|, CALLED iff count >= minHits (:146). The Java
-// loop's early break at the second role changes nothing it reports.
+// (badPeg); else the role with count = |set|, CALLED iff count >= minHits (:146).
+//
+// The Java loop breaks at the second role (:129, `!badPeg`), and so does the probe, a step at a
+// time: an AMBIGUOUS protein reports fid -1 and count 0 and never reaches the tally, so a bucket
+// line fetched for it once two fids are on record is a request the result does not use. At the
+// top of every step each wave reads the block's records into a mask of its dead proteins
+// (dead_mask); a dead protein's windows take the "does not probe" path (bucket 0, served from
+// cache), its queued walks are dropped at flush time and its list is not deduplicated. The
+// records only move apart, so a wave that sees a protein dead sees a fact that stays true, and
+// one that sees it late only probes what it could have skipped: no synchronisation, and the
+// outputs do not depend on timing because a dead protein's outputs are constants.
 //
 // Sets: ceil(1.5 x windows) u32 entries (load <= 2/3 however many windows hit) from the
 // block's LDS pool, greedily in protein order; a protein that does not fit uses its own region
@@ -462,7 +471,8 @@ __device__ __forceinline__ void record_hit(ProteinSmem<P>& sm, const ProteinArgs
 // every kGlobalSet protein's list, counted into pcnt. A list of fewer than kSetPool hits is
 // deduplicated in the pool (the usual case: it needs 2,730+ windows to have that many); a
 // longer one (giant proteins) in a hash set of L entries in the second half of its region,
-// zeroed here (agent-scope stores, the CAS inserts are agent-scope). Block-uniform loop.
+// zeroed here (agent-scope stores, the CAS inserts are agent-scope). The list of a protein that
+// ended AMBIGUOUS is not read: its count is not reported. Block-uniform loop.
 // (Protein bounds from LDS: indexing the kernel's register copy pb[] by the loop counter makes
 // the compiler spill it to scratch.)
 template <int P>
@@ -471,6 +481,7 @@ __device__ __forceinline__ void dedupe_lists(ProteinSmem<P>& sm, const ProteinAr
   const int t = threadIdx.x;
   for (int p = 0; p < P; ++p) {
     if (sm.pset[p] != kGlobalSet) continue;
+    if (sm.pmin[p] != sm.pmax[p]) continue;  // AMBIGUOUS (final here): its count is not reported
     const uint32_t h = sm.plist[p], b0 = sm.pbeg[p];
     if (h == 0) continue;
     const uint32_t* list = a.gset + 2 * (span_lo + b0);
@@ -493,6 +504,24 @@ __device__ __forceinline__ void dedupe_lists(ProteinSmem<P>& sm, const ProteinAr
     if ((t & 63) == 0 && fresh) atomicAdd(&sm.pcnt[p], fresh);
     __syncthreads();  // the pool (or the set) is free for the next list
   }
+}
+
+// The block's dead proteins, bit p for protein p: two different fids are on record, so the
+// protein ends AMBIGUOUS whatever else it hits. Wave-uniform (a ballot: scalar registers).
+// `mx > mn`, not `mn != mx`: a hit lowers pmin before it raises pmax, so a first hit seen
+// between its two atomics reads mn = fid, mx = 0 (the initial value), which is no second fid.
+// mx > mn >= 0 makes mx a recorded fid, and mn (below the initial 0xFFFFFFFF) another.
+//
+// The lane index comes from mbcnt inside the asm, which is not moved out of the step loop: a
+// lane index (or the record's LDS address) held in a register across the step's bucket loads
+// is one register more than the stream kernels have at 7 waves per SIMD (they spilled).
+template <int P>
+__device__ __forceinline__ uint32_t dead_mask(const ProteinSmem<P>& sm) {
+  uint32_t lane;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+  const uint32_t i = lane < (uint32_t)P ? lane : 0u;
+  const uint32_t mn = sm.pmin[i], mx = sm.pmax[i];
+  return (uint32_t)__ballot(lane < (uint32_t)P && mx > mn);
 }
 
 // Which of the block's proteins holds span position x (pb: the block-uniform starts, in
@@ -747,10 +776,12 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
 #ifdef KMA_TUNE_COUNT
     uint32_t wsum = 0, wmax = 0;
 #endif
+    const uint32_t dead_now = dead_mask<P>(sm);  // (a later look than the entries' own steps')
     for (uint32_t e = lane; e < cn; e += 64) {
       const uint32_t w2 = cq[2 * e + 1];
       const uint64_t key = (uint64_t)(w2 & 0xFFu) << 32 | cq[2 * e];
       const uint32_t p = w2 >> 8;
+      if (dead_now >> p & 1u) continue;  // no alternate bucket is requested for a dead protein
       uint32_t fid = 0, sid = 0;
 #ifdef KMA_TUNE_COUNT
       uint32_t walked = 0;
@@ -867,6 +898,7 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
         record_hit<P>(sm, a, span_lo, multiset, c.bk[j] >> kBucketBits, w & kFidMask,
                       (c.bk[j] & kBucketIdx) * kSlotsPerBucket + ((w >> kSlotShift) & kSlotMask));
       // rare: the home bucket missed and the key's filter positions are set -> deferred walk
+      // (never for a protein dead at the top of the step: its windows are not `probed`)
 #ifdef KMA_TUNE_NO_WALK  // tuning builds only (cost bound of the chain walks; misses keys)
       const bool pend = false;
 #else
@@ -888,6 +920,13 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
   // profiles/r03_ab/r03h_steps.log.)
   if (!Packed) load_residues(0u);
   for (uint32_t x0 = 0; x0 < span; x0 += stride) {
+    // A protein dead by now (dead_mask) has no windows from here on: pe[i] = pb[i] makes
+    // window_at false for every x of protein i and changes it for no other x (x of a later
+    // protein is >= both, x of an earlier one below both), so the skip costs a window nothing:
+    // it takes the "does not probe" path of prep. Scalar selects, no register of its own.
+    const uint32_t dead = dead_mask<P>(sm);
+#pragma unroll
+    for (int i = 0; i < P; ++i) pe[i] = dead >> i & 1u ? pb[i] : pe[i];
     Prep cur;
     prep(x0, cur);
     // The next step opens a new stage: its residue words are requested ahead of the bucket
