@@ -397,19 +397,28 @@ constexpr int kWavesPerBlock = 4;
 #define KMA_PROTEIN_OCC 7
 #endif
 constexpr int kProteinOcc = KMA_PROTEIN_OCC;
-// The ASCII kernel's stage: a block packs kStageRes + 7 residues of its span at a time (whole
-// 8-residue groups, 5 bytes each) into the tail of its LDS pool and reads its windows from
-// there, as the packed kernel reads them from the stream. A multiple of a probe step's windows,
-// so a step never straddles two stages; the tail is rounded to the pool's 16-byte zeroing unit,
-// which also covers the second aligned word of the last window's read.
-#ifndef KMA_STAGE_RES
-#define KMA_STAGE_RES 1024
-#endif
-constexpr int kStageRes = KMA_STAGE_RES;
-constexpr int kStageGroups = kStageRes / 8 + 1;
+// The probe's step order (annotate_block): a step is kStepSlots chunks of 64 consecutive span
+// positions, one per (window j of the lane, wave): slot r = kWavesPerBlock j + wave. A span of T
+// steps (T = ceil(span / windows per step)) has chunks [0, kStepSlots T); slot r takes chunk
+// r T + s in step s, so every slot walks its own contiguous part of the span and every step
+// samples the whole span: a protein that turns AMBIGUOUS is seen dead by the steps that follow
+// while most of its windows are still ahead. T = 1 is the plain front-to-back order.
+constexpr int kStepSlots = kWavesPerBlock * kProbeWin;
+// The ASCII kernel's stage: a block packs the residues of kStageSteps consecutive steps (s, s + 1,
+// s even) into the tail of its LDS pool and reads its windows from there, as the packed kernel
+// reads them from the stream. One region per slot: the 64 kStageSteps + 7 residues from span
+// position 64 (r T + s), as whole 8-residue groups of 5 bytes; the regions lie back to back, so
+// the stage is one stream of kStageGroups groups and window w of slot r in step s + d is its
+// residue kRegionRes r + 64 d + w. The tail is rounded to the pool's 16-byte zeroing unit, which
+// also covers the second aligned word of the last window's read.
+constexpr int kStageSteps = 2;
+constexpr int kRegionGroups = 64 * kStageSteps / 8 + 1;
+constexpr int kRegionRes = 8 * kRegionGroups;
+constexpr int kStageGroups = kStepSlots * kRegionGroups;
 constexpr int kStageEntries = (5 * kStageGroups + 15) / 16 * 4;  // u32 pool entries
-static_assert(kStageRes % (256 * kProbeWin) == 0, "a stage holds whole probe steps");
-static_assert(4 * kStageEntries >= 5 * kStageRes / 8 + 8, "the last window reads two aligned words");
+static_assert(4 * kStageEntries >=
+                  5 * (kRegionRes * (kStepSlots - 1) + 64 * kStageSteps - 1) / 8 / 8 * 8 + 16,
+              "the last window reads two aligned words");
 static_assert(kStageEntries < kSetPool / 2, "the stage leaves most of the pool to the sets");
 
 struct ProteinArgs {

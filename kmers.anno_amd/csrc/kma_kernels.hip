@@ -467,6 +467,16 @@ __device__ __forceinline__ void record_hit(ProteinSmem<P>& sm, const ProteinArgs
   if (fresh) atomicAdd(&sm.pcnt[p], 1u);
 }
 
+// The lane's index in its wave, computed where it is used: the probe loop of annotate_block has
+// no register to carry it (or the thread index it comes from) across a step's bucket loads at
+// 7 waves per SIMD, and the compiler spills such a value to scratch memory rather than compute
+// it again. (volatile: not hoisted out of the loop, not merged with threadIdx.)
+__device__ __forceinline__ uint32_t lane_id() {
+  uint32_t lane;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+  return lane;
+}
+
 // After the probe steps (the LDS sets are final, the pool is free): the distinct slot ids of
 // every kGlobalSet protein's list, counted into pcnt. A list of fewer than kSetPool hits is
 // deduplicated in the pool (the usual case: it needs 2,730+ windows to have that many); a
@@ -477,8 +487,7 @@ __device__ __forceinline__ void record_hit(ProteinSmem<P>& sm, const ProteinArgs
 // the compiler spill it to scratch.)
 template <int P>
 __device__ __forceinline__ void dedupe_lists(ProteinSmem<P>& sm, const ProteinArgs& a,
-                                             uint64_t span_lo) {
-  const int t = threadIdx.x;
+                                             uint64_t span_lo, const int t) {
   for (int p = 0; p < P; ++p) {
     if (sm.pset[p] != kGlobalSet) continue;
     if (sm.pmin[p] != sm.pmax[p]) continue;  // AMBIGUOUS (final here): its count is not reported
@@ -512,13 +521,12 @@ __device__ __forceinline__ void dedupe_lists(ProteinSmem<P>& sm, const ProteinAr
 // between its two atomics reads mn = fid, mx = 0 (the initial value), which is no second fid.
 // mx > mn >= 0 makes mx a recorded fid, and mn (below the initial 0xFFFFFFFF) another.
 //
-// The lane index comes from mbcnt inside the asm, which is not moved out of the step loop: a
-// lane index (or the record's LDS address) held in a register across the step's bucket loads
+// The lane index comes from lane_id's mbcnt, which is not moved out of the step loop: a lane
+// index (or the record's LDS address) held in a register across the step's bucket loads
 // is one register more than the stream kernels have at 7 waves per SIMD (they spilled).
 template <int P>
 __device__ __forceinline__ uint32_t dead_mask(const ProteinSmem<P>& sm) {
-  uint32_t lane;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+  const uint32_t lane = lane_id();
   const uint32_t i = lane < (uint32_t)P ? lane : 0u;
   const uint32_t mn = sm.pmin[i], mx = sm.pmax[i];
   return (uint32_t)__ballot(lane < (uint32_t)P && mx > mn);
@@ -546,16 +554,28 @@ __device__ __forceinline__ bool window_at(const uint32_t (&pe)[P], uint32_t x, u
   return ended == p;
 }
 
-// The lane's window within each 256-window slice. KMA_LANE_PERM: quad q's member p takes
-// window 16 p + q of its wave, so that load instruction r (member r of every quad) reads the
-// buckets of 16 consecutive windows — windows that share a minimizer then share a line inside
-// one instruction.
-__device__ __forceinline__ uint32_t lane_window(int t) {
+// The lane's window within its wave's 64-position chunk. KMA_LANE_PERM: quad q's member p takes
+// window 16 p + q, so that load instruction r (member r of every quad) reads the buckets of 16
+// consecutive windows — windows that share a minimizer then share a line inside one
+// instruction.
+__device__ __forceinline__ uint32_t chunk_window(int t) {
 #if KMA_LANE_PERM
-  return (uint32_t)((t >> 6) * 64 + 16 * (t & 3) + ((t & 63) >> 2));
+  return (uint32_t)(16 * (t & 3) + ((t & 63) >> 2));
 #else
-  return (uint32_t)t;
+  return (uint32_t)(t & 63);
 #endif
+}
+// The first span position of slot r's chunk in step s of a span of T steps (kma_internal.h).
+__device__ __forceinline__ uint32_t chunk_pos(uint32_t r, uint32_t T, uint32_t s) {
+  return 64u * (r * T + s);
+}
+// A wave-uniform value the compiler may not take apart: left to itself it splits a step's
+// position `scalar(slot, step) + lane's window` into a loop-invariant vector register per
+// window of the lane (slot part + lane's window) and a scalar step part, which is two registers
+// more than the one lane's window, and the probe loop has none to spare at 7 waves per SIMD.
+__device__ __forceinline__ uint32_t scalar_whole(uint32_t v) {
+  asm volatile("" : "+s"(v));
+  return v;
 }
 
 // A group's inputs that precede its first probe step: its proteins, the offsets wave 0 reads
@@ -584,6 +604,7 @@ __device__ __forceinline__ uint32_t xcd_group(uint32_t b, uint32_t n) {
 
 struct GroupHead {
   uint32_t p0, np;
+  uint32_t steps;  // T: the span's probe steps (the step order needs it for the first residues)
   uint64_t beg_raw;
   uint64_t span_lo;
 };
@@ -592,7 +613,10 @@ __device__ __forceinline__ void head_offsets(const ProteinArgs& a, uint32_t g, G
   h.p0 = g * a.block_proteins;  // g < n_groups: p0 < n_seq
   h.np = min(a.block_proteins, a.n_seq - h.p0);
   h.beg_raw = wave == 0 && lane <= (int)h.np ? a.offsets[h.p0 + lane] : 0u;
-  h.span_lo = a.offsets[h.p0] - a.offsets[0];
+  // (both ends of the span: block-uniform loads issued together, no further round trip)
+  const uint64_t lo = a.offsets[h.p0], hi = a.offsets[h.p0 + h.np];
+  h.span_lo = lo - a.offsets[0];
+  h.steps = (uint32_t)((hi - lo + 256u * kProbeWin - 1u) / (256u * kProbeWin));
 }
 // Window x of the span is at position x + pos0 of `res`. ASCII residues: `res` is the aligned
 // word at or below the span's first byte (d_residues is 8-byte aligned) and pos0 < 8 the byte
@@ -613,48 +637,55 @@ __device__ __forceinline__ const uint8_t* head_res(const ProteinArgs& a, const G
 // its end; windows past the span are masked in the loop).
 template <int U>
 __device__ __forceinline__ void head_residues(const ProteinArgs& a, const GroupHead& h,
-                                              uint32_t tw, WinWords (&ww)[U]) {
+                                              uint32_t wave, uint32_t cw, WinWords (&ww)[U]) {
   uint64_t pos0;
   const uint8_t* res = head_res<true>(a, h, pos0);
   const uint64_t lim = a.n_residues - h.span_lo;
 #pragma unroll
   for (int j = 0; j < U; ++j) {
-    const uint32_t x = j * 256u + tw;
+    const uint32_t x = chunk_pos(kWavesPerBlock * j + wave, h.steps, 0u) + cw;
     ww[j] = window_words_packed(res, (x < lim ? x : 0u) + pos0);
   }
 }
 
-// The ASCII kernel's stage (kma_internal.h): the block's thread t takes the 8-residue groups t,
-// t + 256, .. of the stage at span position xc (a multiple of kStageRes). Group g is the span's
-// residues [xc + 8 g, xc + 8 g + 8): the two aligned words around them, funnelled as a window's
-// bytes are (`res` and `sh` from head_res<false>). Only groups that start below `lim` (the
-// span's length, or what is left of the batch while the span is not known yet) are read, so
-// the last word read is the one the last window's own ASCII load would read; the others read
-// the span's first words and are stored as zero groups. The words wait in the lane's window
-// registers ww[i].lo / .hi, which are free between a step's keys and the next step's windows:
-// registers of their own spilled at 7 waves per SIMD.
+// The ASCII kernel's stage (kma_internal.h) for steps s, s + 1 (s even) of a span of T steps: the
+// block's thread t takes the 8-residue groups t, t + 256, .. of the stage. Group g is group
+// g % kRegionGroups of slot g / kRegionGroups' region: the span's residues [x, x + 8) from
+// stage_group_pos (a multiple of 8, so one funnel shift serves every group): the two aligned
+// words around them, funnelled as a window's bytes are (`res` and `sh` from head_res<false>).
+// Only groups that start below `lim` (the span's length, or what is left of the batch while the
+// span is not known yet) are read, so the last word read is the one the last window's own ASCII
+// load would read; the others (the regions of slots whose chunks lie past the span among them)
+// read the span's first words and are stored as zero groups. The words wait in the lane's
+// window registers ww[i].lo / .hi, which are free between a step's keys and the next step's
+// windows: registers of their own spilled at 7 waves per SIMD.
 constexpr int kStagePerThread = (kStageGroups + 255) / 256;
 static_assert(kStagePerThread <= kProbeWin, "a lane's stage words wait in its window registers");
-__device__ __forceinline__ void stage_fetch(const uint8_t* __restrict__ res, uint32_t xc,
-                                            uint32_t lim, WinWords (&ww)[kProbeWin]) {
-  const uint64_t* words = reinterpret_cast<const uint64_t*>(res) + (xc >> 3);
+__device__ __forceinline__ uint32_t stage_group_pos(uint32_t g, uint32_t T, uint32_t s) {
+  const uint32_t r = g / (uint32_t)kRegionGroups;
+  return chunk_pos(r, T, s) + 8u * (g - r * (uint32_t)kRegionGroups);
+}
+__device__ __forceinline__ void stage_fetch(const uint8_t* __restrict__ res, uint32_t T,
+                                            uint32_t s, uint32_t lim, WinWords (&ww)[kProbeWin]) {
+  const uint64_t* words = reinterpret_cast<const uint64_t*>(res);
 #pragma unroll
   for (int i = 0; i < kStagePerThread; ++i) {
     const uint32_t g = threadIdx.x + 256u * i;
-    const bool in = g < (uint32_t)kStageGroups && xc < lim && 8u * g < lim - xc;
-    const uint64_t* src = in ? words + g : reinterpret_cast<const uint64_t*>(res);
+    const uint32_t x = stage_group_pos(g, T, s);
+    const bool in = g < (uint32_t)kStageGroups && x < lim;
+    const uint64_t* src = words + (in ? x >> 3 : 0u);
     ww[i].lo = src[0];
     ww[i].hi = src[1];
   }
 }
 __device__ __forceinline__ void stage_store(uint8_t* stage, const uint8_t* lut, uint32_t sh,
-                                            uint32_t xc, uint32_t lim,
+                                            uint32_t T, uint32_t s, uint32_t lim,
                                             const WinWords (&ww)[kProbeWin]) {
 #pragma unroll
   for (int i = 0; i < kStagePerThread; ++i) {
     const uint32_t g = threadIdx.x + 256u * i;
     if (g < (uint32_t)kStageGroups) {
-      const bool in = xc < lim && 8u * g < lim - xc;
+      const bool in = stage_group_pos(g, T, s) < lim;
       store40(stage + 5u * g, in ? pack8(lut, funnel(ww[i].lo, ww[i].hi, sh)) : 0u);
     }
   }
@@ -666,12 +697,18 @@ __device__ __forceinline__ void stage_store(uint8_t* stage, const uint8_t* lut, 
 // (pass 0) / short (pass 1: fewer than defer_below probe steps); pass -1: always. sm.lut is
 // being loaded (read after the first barrier).
 //
-// ASCII residues (!Packed) are packed once per block into the stage, the last kStageEntries
-// entries of the pool (the sets take the rest), and every window then reads its key from
-// there exactly as the packed kernel reads it from the stream: two 8-byte LDS reads and a
-// funnel. The first stage is stored between the prologue's barriers; a span longer than
-// kStageRes stores the next one every kStageRes / (256 kProbeWin) steps between two block
-// barriers of its own (the loop's bounds are block-uniform).
+// Step order (kma_internal.h): the span's T = h.steps steps each take one 64-position chunk per
+// slot r = kWavesPerBlock j + wave, chunk r T + s in step s, so a step samples the whole span
+// and the dead mask at the top of a step spares a protein that turned AMBIGUOUS the windows
+// every slot still has ahead of it. Inside a chunk, and in everything indexed by the span
+// position x, nothing depends on the order.
+//
+// ASCII residues (!Packed) are packed into the stage, the last kStageEntries entries of the
+// pool (the sets take the rest), and every window then reads its key from there exactly as the
+// packed kernel reads it from the stream: two 8-byte LDS reads and a funnel. The first stage
+// is stored between the prologue's barriers; a span of more than kStageSteps steps stores the
+// next one every kStageSteps steps between two block barriers of its own (the loop's bounds
+// are block-uniform).
 template <int K, int M, int P, bool Packed>
 __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem<P>& sm,
                                                const GroupHead& h, WinWords (&ww)[kProbeWin],
@@ -680,7 +717,15 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
   constexpr int U = kProbeWin;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, part = t & 3;
   const bool multiset = (a.flags & KMA_F_MULTISET) != 0;
-  const uint32_t tw = lane_window(t);
+  const uint32_t T = h.steps;
+  // A window's position is chunk_pos(kWavesPerBlock j + wv, T, s) + cw: a scalar and the lane's
+  // one register. The ASCII kernel needs the lane's window by itself for the stage, so its
+  // wave's term is in the scalar (wv: the wave, in a scalar register); the stream kernels put
+  // it into the lane's register, as the position had it before the strided order (wv = 0): they
+  // are the first to spill.
+  const uint32_t ws = (uint32_t)__builtin_amdgcn_readfirstlane(wave);
+  const uint32_t wv = Packed ? 0u : ws;
+  const uint32_t cw = chunk_window(t) + (Packed ? chunk_pos((uint32_t)wave, T, 0u) : 0u);
   const uint32_t p0 = h.p0, np = h.np;
   const uint64_t beg_raw = h.beg_raw, span_lo = h.span_lo;
   const uint64_t o0 = a.offsets[0];
@@ -741,7 +786,7 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
   uint8_t* stage = reinterpret_cast<uint8_t*>(sm.pool + kPool);
   const uint32_t stage_sh = (uint32_t)pos0 * 8u;
   // the first stage: beside the zeroing of the sets below it, read after the third barrier
-  if (!Packed) stage_store(stage, sm.lut, stage_sh, 0u, a.n_residues - (uint32_t)span_lo, ww);
+  if (!Packed) stage_store(stage, sm.lut, stage_sh, T, 0u, a.n_residues - (uint32_t)span_lo, ww);
   const uint32_t used = sm.chain_q[0][0];
   uint32_t pb[P + 1], pe[P];
 #pragma unroll
@@ -758,9 +803,8 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
   const uint64_t* __restrict__ slots = a.slots;
   const uint32_t nb = a.n_buckets;
   const bool two_choice = a.two_choice != 0;
-  uint32_t* cq = sm.chain_q[wave];
+  uint32_t* cq = sm.chain_q[ws];
   uint32_t cn = 0;  // wave-uniform queue length
-  constexpr uint32_t stride = 256u * U;
   // Deferred chain walks, 64 queued windows at a time: lane (quad g, member p) takes entry
   // 16 p + g of the chunk; the chain's first bucket of every entry is loaded and matched by a
   // quad (the probe loop's cooperative loads: 2 line requests per bucket instead of 8 dwordx4
@@ -777,7 +821,7 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
     uint32_t wsum = 0, wmax = 0;
 #endif
     const uint32_t dead_now = dead_mask<P>(sm);  // (a later look than the entries' own steps')
-    for (uint32_t e = lane; e < cn; e += 64) {
+    for (uint32_t e = lane_id(); e < cn; e += 64) {
       const uint32_t w2 = cq[2 * e + 1];
       const uint64_t key = (uint64_t)(w2 & 0xFFu) << 32 | cq[2 * e];
       const uint32_t p = w2 >> 8;
@@ -817,10 +861,11 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
   struct Prep {
     uint32_t klo[U], khi[U], need[U], bk[U];
   };
-  auto prep = [&](uint32_t xs, Prep& o) {
+  auto prep = [&](uint32_t s, Prep& o) {
 #pragma unroll
     for (int j = 0; j < U; ++j) {
-      const uint32_t x = xs + j * 256u + tw;
+      const uint32_t xc = chunk_pos(kWavesPerBlock * j + wv, T, s);
+      const uint32_t x = (Packed ? xc : scalar_whole(xc)) + cw;
       const uint32_t p = protein_at<P>(pb, x);
       // (key 0: every residue without a code; it would match an empty slot)
       const uint64_t key = packed_key<K>(ww[j]);
@@ -849,18 +894,21 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
       }
     }
   };
-  auto load_residues = [&](uint32_t xs) {
+  auto load_residues = [&](uint32_t s) {
 #pragma unroll
     for (int j = 0; j < U; ++j) {
-      const uint32_t x = xs + j * 256u + tw;
-      if (Packed)
+      const uint32_t r = kWavesPerBlock * j + wv;
+      if (Packed) {
+        const uint32_t x = chunk_pos(r, T, s) + cw;
         ww[j] = window_words_packed(res, (x < span ? x : 0u) + pos0);
-      else  // (x's stage is the one in LDS; a step past the span reads stale groups, masked)
-        ww[j] = window_words_packed(stage, x % (uint32_t)kStageRes);
+      } else {  // (s's stage is the one in LDS; a step past the span reads stale groups, masked)
+        const uint32_t at = (uint32_t)kRegionRes * r + 64u * (s % (uint32_t)kStageSteps);
+        ww[j] = window_words_packed(stage, scalar_whole(at) + cw);
+      }
     }
   };
   // Compare the quad's buckets, record hits, queue chain walks.
-  auto settle = [&](uint32_t x0, const Prep& c, const uint4 (&q)[U][4][kBucketHalves]) {
+  auto settle = [&](const Prep& c, const uint4 (&q)[U][4][kBucketHalves]) {
     uint32_t word[U];
 #pragma unroll
     for (int j = 0; j < U; ++j) {
@@ -919,7 +967,7 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
   // pipeline packing step i + 1 under step i's gather measured 6.51 vs 4.48 ms at c5,
   // profiles/r03_ab/r03h_steps.log.)
   if (!Packed) load_residues(0u);
-  for (uint32_t x0 = 0; x0 < span; x0 += stride) {
+  for (uint32_t s = 0; s < T; ++s) {
     // A protein dead by now (dead_mask) has no windows from here on: pe[i] = pb[i] makes
     // window_at false for every x of protein i and changes it for no other x (x of a later
     // protein is >= both, x of an earlier one below both), so the skip costs a window nothing:
@@ -928,36 +976,39 @@ __device__ __forceinline__ void annotate_block(const ProteinArgs& a, ProteinSmem
 #pragma unroll
     for (int i = 0; i < P; ++i) pe[i] = dead >> i & 1u ? pb[i] : pe[i];
     Prep cur;
-    prep(x0, cur);
+    prep(s, cur);
     // The next step opens a new stage: its residue words are requested ahead of the bucket
     // loads and stored under them. Every wave has taken this step's windows from the old stage
     // once it is past prep, hence the first barrier. (Stored after settle instead: c5 2.768 vs
     // 2.751 ms)
-    const uint32_t xn = x0 + stride;
-    const bool restage = !Packed && xn % (uint32_t)kStageRes == 0u && xn < span;  // block-uniform
-    if (restage) stage_fetch(res, xn, span, ww);
+    const uint32_t sn = s + 1u;
+    const bool restage = !Packed && sn % (uint32_t)kStageSteps == 0u && sn < T;  // block-uniform
+    if (restage) stage_fetch(res, T, sn, span, ww);
     uint4 q[U][4][kBucketHalves];
     gather(cur, q);
     // next step's residues (issued after the bucket loads: waiting for those leaves these in
     // flight, vmcnt counts in order)
-    if (Packed) load_residues(xn);  // (past the span: clamped to its first word)
+    if (Packed) load_residues(sn);  // (past the span: clamped to its first word)
     if (restage) {  // (under the bucket loads: its words arrive first, the barriers wait with them)
       __syncthreads();
-      stage_store(stage, sm.lut, stage_sh, xn, span, ww);
+      stage_store(stage, sm.lut, stage_sh, T, sn, span, ww);
       __syncthreads();
     }
-    settle(x0, cur, q);
+    settle(cur, q);
     // (from the stage: an LDS round trip, not worth ten registers held across the buckets)
-    if (!Packed) load_residues(xn);
-    if (x0 == 0) KMA_CLK(2);
+    if (!Packed) load_residues(sn);
+    if (s == 0) KMA_CLK(2);
   }
   KMA_CLK(3);
-  KMA_CLK_SET(7, (span + stride - 1) / stride);
+  KMA_CLK_SET(7, T);
   if (cn) chain_flush();
   KMA_CLK(4);
   __syncthreads();  // every LDS set is final; the lists are complete
-  if (!multiset) dedupe_lists<P>(sm, a, span_lo);
-  if (t < (int)np) {
+  // (the thread index again, from the wave and the lane: see lane_id)
+  const int te = (int)(64u * ws + lane_id());
+  if (!multiset) dedupe_lists<P>(sm, a, span_lo, te);
+  if (te < (int)np) {
+    const int t = te;
     const uint32_t mn = sm.pmin[t], mx = sm.pmax[t], cnt = sm.pcnt[t];
     int32_t fid_out = -1, cnt_out = 0;
     uint8_t st;
@@ -1005,11 +1056,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(protein_occ
   const uint32_t b = blockIdx.x - (second ? a.n_groups : 0u);
   head_offsets(a, a.defer_below ? b : xcd_group(b, a.n_groups), h);
   if (Packed) {
-    head_residues<kProbeWin>(a, h, lane_window(t), ww);
+    head_residues<kProbeWin>(a, h, (uint32_t)t >> 6, chunk_window(t), ww);
   } else {  // the first stage's residue words (clamped to the batch: the span is not known yet)
     uint64_t pos0;
     const uint8_t* res = head_res<false>(a, h, pos0);
-    stage_fetch(res, 0u, a.n_residues - (uint32_t)h.span_lo, ww);  // (span_lo <= n_residues)
+    stage_fetch(res, h.steps, 0u, a.n_residues - (uint32_t)h.span_lo, ww);  // (span_lo <= n_residues)
     sm.lut[t] = lut_b;
   }
   annotate_block<K, M, P, Packed>(a, sm, h, ww, a.defer_below ? (second ? 1 : 0) : -1);

@@ -10,7 +10,10 @@ generator), looks every window up in the table on the CPU (a sorted-key search: 
 every window, -1 for a miss) and applies the library's own block assignment: proteins
 [g P, g P + P) form block g (P = 6 for c5, 4 for c4 and c2: kma_abi.cpp's block_proteins),
 window i of a protein that starts `base` residues into its block's span is span position
-base + i, and a step takes 512 consecutive span positions (256 threads x 2).
+base + i. "Library order" below is the probe's order up to DESIGN 5.7: a step takes 512
+consecutive span positions (256 threads x 2). The order the kernel has now is the
+strided one: a block of T = ceil(span / 512) steps has 64-position chunks [0, 8 T), and step s
+takes chunks r T + s, r = 0..7, so span position x is probed in step (x // 64) % T.
 
 Per protein: i2 = the first window whose fid differs from the protein's first hit's (none: the
 protein is not AMBIGUOUS). Under complete visibility (every hit of steps <= s is on record at
@@ -28,6 +31,11 @@ Printed (one JSON line), as shares of the batch's windows unless said otherwise:
                                           and step, not before ~11 steps; c5's blocks have ~4)
   walk_share                              skipped + dropped: the share of deferred walks that
                                           is not walked (walks taken as uniform over windows)
+  strided_skipped_windows                 the kernel's order (built): a protein's
+                                          dead step is the second smallest, over its distinct
+                                          fids, of the earliest step in which that fid is hit
+                                          (two fids inside one step make it the dead step);
+                                          skipped are its windows in later steps
   interleaved_skipped_windows             for sizing only, not built: the same skip if a block's
                                           steps took every protein's windows in proportion
                                           (window i of w in step floor(i S / w), S the block's
@@ -55,6 +63,33 @@ _CODE[65:91] = np.arange(1, 27)
 _CODE[42] = 27
 
 
+def strided_skipped(base, w, T, hp, hi, hf):
+    """Per protein, the windows the strided step order skips under complete visibility, and the
+    protein's dead step (-1: it never has two fids on record). base, w, T: per protein, its
+    first span position, its windows and its block's steps (>= 1); hp, hi, hf: per hit, its
+    protein, its window index in the protein and its fid."""
+    base, w, T = (np.asarray(v, np.int64) for v in (base, w, T))
+    hp, hi, hf = (np.asarray(v, np.int64) for v in (hp, hi, hf))
+    n = len(base)
+    hs = ((base[hp] + hi) // 64) % T[hp]  # the step that probes the hit's window
+    o = np.lexsort((hs, hf, hp))  # by protein, fid, step: each (protein, fid)'s earliest step
+    p1, f1, s1 = hp[o], hf[o], hs[o]
+    lead = np.ones(len(o), bool)
+    lead[1:] = (p1[1:] != p1[:-1]) | (f1[1:] != f1[:-1])
+    p1, s1 = p1[lead], s1[lead]
+    o = np.lexsort((s1, p1))  # by protein, step: the second row of a protein is its dead step
+    p1, s1 = p1[o], s1[o]
+    second = (np.arange(len(p1)) - np.searchsorted(p1, p1, "left")) == 1
+    dead = np.full(n, -1, np.int64)
+    dead[p1[second]] = s1[second]
+    wstart = np.zeros(n + 1, np.int64)
+    wstart[1:] = np.cumsum(w)
+    pid = np.repeat(np.arange(n), w)
+    ws = ((base[pid] + np.arange(wstart[-1]) - wstart[pid]) // 64) % T[pid]
+    late = (dead[pid] >= 0) & (ws > dead[pid])
+    return np.bincount(pid[late], minlength=n), dead
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("workload", choices=sorted(BLOCK_PROTEINS))
@@ -77,7 +112,7 @@ def main():
     P = args.block_proteins or BLOCK_PROTEINS[args.workload]
     n_blocks = (n_seq + P - 1) // P
     tot = dict.fromkeys(("proteins", "windows", "amb_p", "amb_w", "skip", "drop", "inter",
-                         "called"), 0)
+                         "strided", "called"), 0)
     chunk = 4096 * args.sample  # blocks per pass
     for b0 in range(0, n_blocks, chunk):
         blocks = np.arange(b0, min(b0 + chunk, n_blocks), args.sample)
@@ -122,6 +157,7 @@ def main():
         si = np.where(w > 0, i2 * S // np.maximum(w, 1), 0)
         kept_i = np.minimum(w, -((-(si + 1) * w) // S))  # first i with floor(i S / w) > si
         inter = np.where(amb, w - kept_i, 0)
+        strided, _ = strided_skipped(base, w, S, hp, hi_, hf)
         tot["proteins"] += len(prot)
         tot["windows"] += int(w.sum())
         tot["amb_p"] += int(amb.sum())
@@ -129,6 +165,7 @@ def main():
         tot["skip"] += int(skip.sum())
         tot["drop"] += int((w[amb] - skip[amb]).sum())
         tot["inter"] += int(inter.sum())
+        tot["strided"] += int(strided.sum())
     W = tot["windows"]
     out = {"workload": args.workload, "block_proteins": P, "sample_every": args.sample,
            "proteins": tot["proteins"], "windows": W,
@@ -137,6 +174,7 @@ def main():
            "skipped_windows": tot["skip"] / W,
            "dropped_walk_windows": tot["drop"] / W,
            "walk_share": (tot["skip"] + tot["drop"]) / W,
+           "strided_skipped_windows": tot["strided"] / W,
            "interleaved_skipped_windows": tot["inter"] / W,
            "called": tot["called"], "seconds": round(time.time() - t0, 1)}
     print(json.dumps(out), flush=True)
