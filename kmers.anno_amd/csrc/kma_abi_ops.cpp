@@ -1,0 +1,763 @@
+// kma_abi_ops.cpp — the projector's one-shot set operators of the C ABI (include/kmeranno.h):
+// peg table, signatures, distances / best match, peg proposals, ORF index, translation and
+// hash-annotate. Each checks its arguments on the host, enters its device, stages its batch in
+// buffers of its own (kma_host.h: upload_batch, Scratch, AlphabetFlag), runs its launchers
+// (kma_proposals.hip, kma_distance.hip, kma_hashanno.hip, kma_orf.hip, kma_translate.hip) on
+// the null stream and copies the results back.
+#include <memory>
+
+#include "kma_distance.h"
+#include "kma_hashanno.h"
+#include "kma_internal.h"
+#include "kma_objects.h"
+#include "kma_orf.h"
+#include "kma_translate.h"
+
+using namespace kma::host;
+
+extern "C" {
+
+int kma_peg_table_create(const uint8_t* residues, const uint64_t* offsets, uint32_t n_peg, int k,
+                         int device, double load_factor, kma_table** out,
+                         uint64_t* n_windows) {
+  if (!out) return fail(KMA_E_INVALID, "null argument");
+  *out = nullptr;
+  if (int rc = check_k(k)) return rc;
+  if (load_factor <= 0) load_factor = 0.5;
+  if (load_factor > 0.95) return fail(KMA_E_INVALID, "load factor %.3f > 0.95", load_factor);
+  if (n_peg > KMA_MAX_FID + 1u) return fail(KMA_E_INVALID, "more than 2^22 pegs");
+  if (n_peg && (!residues || !offsets)) return fail(KMA_E_INVALID, "null argument");
+  if (int rc = check_offsets(offsets, n_peg, "", 0, nullptr)) return rc;
+  const uint64_t total = n_peg ? offsets[n_peg] - offsets[0] : 0;
+  uint8_t lut[256];
+  standard_lut(lut);
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  DevBufs b;
+  uint8_t *d_lut, *d_flags;
+  uint64_t *d_keys, *d_keys2, *d_n;
+  uint32_t *d_pegs, *d_pegs2;
+  const uint64_t nw = std::max<uint64_t>(total, 1);
+  KMA_HIP(b.alloc(&d_lut, 256));
+  KMA_HIP(b.alloc(&d_keys, nw * 8));
+  KMA_HIP(b.alloc(&d_keys2, nw * 8));
+  KMA_HIP(b.alloc(&d_pegs, nw * 4));
+  KMA_HIP(b.alloc(&d_pegs2, nw * 4));
+  KMA_HIP(b.alloc(&d_flags, nw));
+  KMA_HIP(b.alloc(&d_n, 8));
+  KMA_HIP(hipMemset(d_n, 0, 8));
+  uint64_t n_sel = 0, windows = 0;
+  if (total) {  // (an empty batch stages nothing: the table is built from no keys)
+    for (uint32_t s = 0; s < n_peg; ++s) {
+      const uint64_t L = offsets[s + 1] - offsets[s];
+      if (L > (uint64_t)k) windows += L - k;
+    }
+    DevBatch in;
+    if (int rc = upload_batch(b, residues, offsets, n_peg, 64, &in)) return rc;
+    KMA_HIP(hipMemcpy(d_lut, lut, 256, hipMemcpyHostToDevice));
+    KMA_HIP(kma::launch_peg_windows(in.bytes, in.off, n_peg, k, d_lut, d_keys, d_pegs, nullptr));
+    Scratch tmp;
+    KMA_HIP(kma::launch_sort_pairs(nullptr, tmp.ask(), d_keys, d_keys2, d_pegs, d_pegs2, total,
+                                   5 * k, nullptr));
+    KMA_HIP(kma::launch_select_flagged(nullptr, tmp.ask(), d_keys2, d_pegs2, d_flags, d_keys,
+                                       d_pegs, d_n, total, nullptr));
+    KMA_HIP(tmp.alloc(b));
+    KMA_HIP(kma::launch_sort_pairs(tmp.p, tmp.bytes(), d_keys, d_keys2, d_pegs, d_pegs2, total,
+                                   5 * k, nullptr));
+    KMA_HIP(kma::launch_singleton_flags(d_keys2, total, d_flags, nullptr));
+    KMA_HIP(kma::launch_select_flagged(tmp.p, tmp.bytes(), d_keys2, d_pegs2, d_flags, d_keys,
+                                       d_pegs, d_n, total, nullptr));
+    KMA_HIP(hipMemcpy(&n_sel, d_n, 8, hipMemcpyDeviceToHost));
+  }
+  if (n_windows) *n_windows = windows;
+  const int rc = create_from_device_keys(d_keys, d_pegs, n_sel, k, device, load_factor, lut, out);
+  if (rc != KMA_OK) return rc;
+  (*out)->info.n_rows = windows;
+  return KMA_OK;
+}
+
+int kma_build_signatures(const uint8_t* residues, const uint64_t* offsets, const int32_t* roles,
+                         uint32_t n_seq, int k, uint32_t flags, int device, uint64_t* out_keys,
+                         uint32_t* out_roles, uint64_t cap, uint64_t* n_out) {
+  if (!n_out) return fail(KMA_E_INVALID, "null argument");
+  *n_out = 0;
+  if (int rc = check_k(k)) return rc;
+  if (flags & ~KMA_F_END_EXCLUSIVE) return fail(KMA_E_INVALID, "bad flags");
+  if (n_seq == 0) return KMA_OK;
+  if (!residues || !offsets || !roles) return fail(KMA_E_INVALID, "null argument");
+  // (not check_offsets: a protein's role is checked on the way, before a later decrease)
+  for (uint32_t s = 0; s < n_seq; ++s) {
+    if (offsets[s + 1] < offsets[s]) return fail(KMA_E_INVALID, "offsets decrease at %u", s);
+    if (roles[s] >= (int32_t)kma::kBuildNeg)
+      return fail(KMA_E_INVALID, "role %d of protein %u >= 2^24 - 1", roles[s], s);
+  }
+  const uint64_t total = offsets[n_seq] - offsets[0];
+  if (total == 0) return KMA_OK;
+  if (total >= (1ull << 31)) return fail(KMA_E_INVALID, "more than 2^31 residues in one call");
+  uint8_t lut[256];
+  standard_lut(lut);
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  DevBufs b;
+  DevBatch in;
+  if (int rc = upload_batch(b, residues, offsets, n_seq, 64, &in)) return rc;
+  uint8_t *d_lut, *d_flags;
+  uint64_t *d_ka, *d_kb, *d_n;
+  int32_t* d_roles;
+  uint32_t *d_ta, *d_tb, *d_head, *d_run;
+  KMA_HIP(b.alloc(&d_roles, n_seq * 4ull));
+  KMA_HIP(b.alloc(&d_lut, 256));
+  KMA_HIP(b.alloc(&d_ka, total * 8));
+  KMA_HIP(b.alloc(&d_kb, total * 8));
+  KMA_HIP(b.alloc(&d_ta, total * 4));
+  KMA_HIP(b.alloc(&d_tb, total * 4));
+  KMA_HIP(b.alloc(&d_head, total * 4));
+  KMA_HIP(b.alloc(&d_run, total * 4));
+  KMA_HIP(b.alloc(&d_flags, total));
+  KMA_HIP(b.alloc(&d_n, 16));
+  KMA_HIP(hipMemcpy(d_roles, roles, n_seq * 4ull, hipMemcpyHostToDevice));
+  KMA_HIP(hipMemcpy(d_lut, lut, 256, hipMemcpyHostToDevice));
+  AlphabetFlag alpha;
+  if (int rc = alpha.init(b)) return rc;
+  KMA_HIP(kma::launch_build_windows(in.bytes, in.off, n_seq, d_roles, k,
+                                    (flags & KMA_F_END_EXCLUSIVE) ? 1 : 0, d_lut, d_ka, d_ta,
+                                    alpha.d, nullptr));
+  // (key, role) pairs sorted by key; RoleCounter per key run; select the good runs' heads
+  Scratch tmp;
+  KMA_HIP(kma::launch_sort_pairs(nullptr, tmp.ask(), d_ka, d_kb, d_ta, d_tb, total, 5 * k,
+                                 nullptr));
+  KMA_HIP(kma::launch_signature_flags(d_kb, d_tb, total, d_flags, d_head, d_run, nullptr,
+                                      tmp.ask(), nullptr));
+  KMA_HIP(kma::launch_select_flagged(nullptr, tmp.ask(), d_kb, d_tb, d_flags, d_ka, d_ta, d_n,
+                                     total, nullptr));
+  KMA_HIP(tmp.alloc(b));
+  KMA_HIP(kma::launch_sort_pairs(tmp.p, tmp.bytes(), d_ka, d_kb, d_ta, d_tb, total, 5 * k,
+                                 nullptr));
+  KMA_HIP(kma::launch_signature_flags(d_kb, d_tb, total, d_flags, d_head, d_run, tmp.p,
+                                      tmp.bytes(), nullptr));
+  KMA_HIP(kma::launch_select_flagged(tmp.p, tmp.bytes(), d_kb, d_tb, d_flags, d_ka, d_ta, d_n,
+                                     total, nullptr));
+  uint64_t n_sel = 0;
+  KMA_HIP(hipMemcpy(&n_sel, d_n, 8, hipMemcpyDeviceToHost));
+  if (int rc = alpha.check()) return rc;
+  *n_out = n_sel;
+  if (n_sel > cap || (n_sel && (!out_keys || !out_roles)))
+    return fail(KMA_E_CAPACITY, "%llu signature kmers, capacity %llu",
+                (unsigned long long)n_sel, (unsigned long long)cap);
+  if (n_sel == 0) return KMA_OK;
+  KMA_HIP(hipMemcpy(out_keys, d_ka, n_sel * 8, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_roles, d_ta, n_sel * 4, hipMemcpyDeviceToHost));
+  return KMA_OK;
+}
+
+// ---- ProteinKmers.distance (GeneCopyProcessor.java:129-162) ------------------------------------
+int kma_protein_distances(const uint8_t* residues, const uint64_t* offsets, uint32_t n_seq, int k,
+                          uint32_t flags, const uint32_t* pair_a, const uint32_t* pair_b,
+                          uint64_t n_pairs, int device, uint32_t* out_sim, uint32_t* out_size,
+                          double* out_dist) {
+  if (k < 2 || k > 12) return fail(KMA_E_INVALID, "kmer size %d outside 2..12", k);
+  if (flags & ~KMA_F_END_EXCLUSIVE) return fail(KMA_E_INVALID, "bad flags");
+  if (n_pairs && (!pair_a || !pair_b || !out_sim)) return fail(KMA_E_INVALID, "null argument");
+  if (n_seq && (!residues || !offsets)) return fail(KMA_E_INVALID, "null argument");
+  for (uint64_t i = 0; i < n_pairs; ++i)
+    if (pair_a[i] >= n_seq || pair_b[i] >= n_seq)
+      return fail(KMA_E_INVALID, "pair %llu indexes a protein >= %u", (unsigned long long)i,
+                  n_seq);
+  if (int rc = check_offsets(offsets, n_seq, "", 1ull << 31,
+                             "more than 2^31 residues in one call"))
+    return rc;
+  if (n_seq == 0 || (n_pairs == 0 && !out_size)) return KMA_OK;
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  DevBufs b;
+  DevBatch in;
+  if (int rc = upload_batch(b, residues, offsets, n_seq, 64, &in)) return rc;
+  uint64_t *d_off = in.off, *d_keys, *d_sorted;
+  uint32_t *d_size, *d_pa, *d_pb, *d_sim;
+  const uint64_t total = in.total;
+  const uint64_t nw = std::max<uint64_t>(total, 1), np = std::max<uint64_t>(n_pairs, 1);
+  KMA_HIP(b.alloc(&d_keys, nw * 8));
+  KMA_HIP(b.alloc(&d_sorted, nw * 8));
+  KMA_HIP(b.alloc(&d_size, n_seq * 4ull));
+  KMA_HIP(b.alloc(&d_pa, np * 4));
+  KMA_HIP(b.alloc(&d_pb, np * 4));
+  KMA_HIP(b.alloc(&d_sim, np * 4));
+  if (n_pairs) {
+    KMA_HIP(hipMemcpy(d_pa, pair_a, n_pairs * 4, hipMemcpyHostToDevice));
+    KMA_HIP(hipMemcpy(d_pb, pair_b, n_pairs * 4, hipMemcpyHostToDevice));
+  }
+  AlphabetFlag alpha;
+  if (int rc = alpha.init(b)) return rc;
+  KMA_HIP(kma::launch_window_keys(in.bytes, d_off, n_seq, k,
+                                  (flags & KMA_F_END_EXCLUSIVE) ? 1 : 0, d_keys, alpha.d, nullptr));
+  Scratch tmp;
+  KMA_HIP(kma::launch_segmented_sort(nullptr, tmp.ask(), d_keys, d_sorted, total, n_seq, d_off,
+                                     d_off + 1, 5 * k, nullptr));
+  KMA_HIP(tmp.alloc(b));
+  KMA_HIP(kma::launch_segmented_sort(tmp.p, tmp.bytes(), d_keys, d_sorted, total, n_seq, d_off,
+                                     d_off + 1, 5 * k, nullptr));
+  KMA_HIP(kma::launch_distinct(d_sorted, d_off, n_seq, d_size, nullptr));
+  if (n_pairs)
+    KMA_HIP(kma::launch_pairs(d_sorted, d_off, d_size, d_sorted, d_off, d_size, d_pa, d_pb,
+                              n_pairs, d_sim, nullptr));
+  if (int rc = alpha.check()) return rc;
+  std::vector<uint32_t> size(n_seq);
+  KMA_HIP(hipMemcpy(size.data(), d_size, n_seq * 4ull, hipMemcpyDeviceToHost));
+  if (out_size) std::memcpy(out_size, size.data(), n_seq * 4ull);
+  if (n_pairs) KMA_HIP(hipMemcpy(out_sim, d_sim, n_pairs * 4, hipMemcpyDeviceToHost));
+  if (out_dist)
+    for (uint64_t i = 0; i < n_pairs; ++i) {
+      // SequenceKmers.distance restated: 1 - similarity / union, 1.0 when nothing is shared
+      const uint32_t sim = out_sim[i];
+      const double uni = (double)size[pair_a[i]] + (double)size[pair_b[i]] - (double)sim;
+      out_dist[i] = sim > 0 ? 1.0 - (double)sim / uni : 1.0;
+    }
+  return KMA_OK;
+}
+
+int kma_protein_best_match(const uint8_t* residues, const uint64_t* offsets, uint32_t n_seq, int k,
+                           uint32_t flags, const uint32_t* query, const uint64_t* cand_off,
+                           const uint32_t* cand, uint32_t n_query, double max_dist, int device,
+                           int32_t* out_best, double* out_best_dist) {
+  if (n_query && (!query || !cand_off || !out_best)) return fail(KMA_E_INVALID, "null argument");
+  const uint64_t n_pairs = n_query ? cand_off[n_query] - cand_off[0] : 0;
+  if (n_pairs && !cand) return fail(KMA_E_INVALID, "null argument");
+  for (uint32_t q = 0; q < n_query; ++q)
+    if (cand_off[q + 1] < cand_off[q]) return fail(KMA_E_INVALID, "cand_off decreases at %u", q);
+  std::vector<uint32_t> pa(n_pairs), pb(n_pairs), sim(n_pairs);
+  std::vector<double> dist(n_pairs);
+  for (uint32_t q = 0; q < n_query; ++q)
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) {
+      pa[i - cand_off[0]] = query[q];
+      pb[i - cand_off[0]] = cand[i];
+    }
+  if (int rc = kma_protein_distances(residues, offsets, n_seq, k, flags, pa.data(), pb.data(),
+                                     n_pairs, device, sim.data(), nullptr, dist.data()))
+    return rc;
+  // GeneCopyProcessor.java:135-146: fDist = maxDist; for each candidate in order,
+  // if (f2Dist <= fDist) { fDist = f2Dist; found = f2; }
+  for (uint32_t q = 0; q < n_query; ++q) {
+    double best = max_dist;
+    int32_t found = -1;
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) {
+      const double d = dist[i - cand_off[0]];
+      if (d <= best) {
+        best = d;
+        found = (int32_t)cand[i];
+      }
+    }
+    out_best[q] = found;
+    if (out_best_dist) out_best_dist[q] = best;
+  }
+  return KMA_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
+
+int kma_propose_pegs(const kma_hit* hits, uint64_t n_hits, const uint32_t* peg_len,
+                     uint32_t n_peg, int k, double min_strength, double max_fuzz,
+                     double min_fuzz, int device, kma_proposal* out, uint64_t cap,
+                     uint64_t* n_out, uint64_t* stats) {
+  if (!n_out || !stats) return fail(KMA_E_INVALID, "null argument");
+  if (int rc = check_k(k)) return rc;
+  *n_out = 0;
+  stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (n_hits == 0) return KMA_OK;
+  if (!hits || !peg_len || n_peg == 0) return fail(KMA_E_INVALID, "null argument");
+  if (cap && !out) return fail(KMA_E_INVALID, "null output");
+  if (n_hits >= (1ull << 31)) return fail(KMA_E_INVALID, "more than 2^31 connections");
+  if ((uint64_t)n_peg * 6 >= (1ull << 32)) return fail(KMA_E_INVALID, "too many pegs");
+  for (uint64_t i = 0; i < n_hits; ++i) {
+    const kma_hit& h = hits[i];
+    if (h.fid >= n_peg) return fail(KMA_E_INVALID, "connection %llu: peg %u >= %u",
+                                    (unsigned long long)i, h.fid, n_peg);
+    if (h.strand != '+' && h.strand != '-')
+      return fail(KMA_E_INVALID, "connection %llu: strand must be '+' or '-'",
+                  (unsigned long long)i);
+    if (i && (h.contig < hits[i - 1].contig ||
+              (h.contig == hits[i - 1].contig && h.left < hits[i - 1].left)))
+      return fail(KMA_E_INVALID, "connections are not in (contig, left) order at %llu",
+                  (unsigned long long)i);
+  }
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  const uint64_t n = n_hits;
+  DevBufs b;
+  kma::PropArgs a{};
+  kma_hit* d_hits;
+  uint32_t* d_len;
+  KMA_HIP(b.alloc(&d_hits, n * sizeof(kma_hit)));
+  KMA_HIP(b.alloc(&d_len, n_peg * 4ull));
+  for (uint32_t** p : {&a.keys, &a.skeys, &a.idx, &a.sidx, &a.head, &a.list_no, &a.scontig,
+                       &a.keep, &a.evidence, &a.out_pos})
+    KMA_HIP(b.alloc(p, n * 4));
+  KMA_HIP(b.alloc(&a.starts, (n + 1) * 4));
+  KMA_HIP(b.alloc(&a.sleft, n * 4));
+  KMA_HIP(b.alloc(&a.best, n * 4));
+  KMA_HIP(b.alloc(&a.stats, 32));
+  KMA_HIP(b.alloc(&a.out, n * sizeof(kma_proposal)));
+  a.hits = d_hits;
+  a.n = (uint32_t)n;
+  a.peg_len = d_len;
+  a.n_peg = n_peg;
+  a.k = k;
+  a.min_strength = min_strength;
+  a.max_fuzz = max_fuzz;
+  a.min_fuzz = min_fuzz;
+  a.cap = n;
+  Scratch tmp;
+  KMA_HIP(kma::launch_propose(a, nullptr, tmp.ask(), nullptr));
+  KMA_HIP(tmp.alloc(b));
+  KMA_HIP(hipMemcpy(d_hits, hits, n * sizeof(kma_hit), hipMemcpyHostToDevice));
+  KMA_HIP(hipMemcpy(d_len, peg_len, n_peg * 4ull, hipMemcpyHostToDevice));
+  KMA_HIP(hipMemset(a.stats, 0, 32));
+  KMA_HIP(kma::launch_propose(a, tmp.p, tmp.bytes(), nullptr));
+  KMA_HIP(hipMemcpy(stats, a.stats, 32, hipMemcpyDeviceToHost));
+  *n_out = stats[3];
+  const uint64_t take = std::min<uint64_t>(stats[3], cap);
+  if (take) KMA_HIP(hipMemcpy(out, a.out, take * sizeof(kma_proposal), hipMemcpyDeviceToHost));
+  if (stats[3] > cap)
+    return fail(KMA_E_CAPACITY, "%llu proposals, capacity %llu", (unsigned long long)stats[3],
+                (unsigned long long)cap);
+  return KMA_OK;
+}
+
+}  // extern "C"
+
+// ---- ORF index of the projector (kma_orf.hip) ---------------------------------------------------
+// One genome's stop / start scans on one device. Immutable after creation: kma_extend_proposals
+// only reads it and stages every call in buffers of its own, so calls may run concurrently.
+struct kma_orf_index {
+  int device = 0;
+  uint32_t n_contig = 0;
+  int32_t* len = nullptr;      // device: n_contig contig lengths
+  uint64_t* hoff = nullptr;    // device: n_contig + 1 per-strand slot offsets
+  uint32_t* stop_at = nullptr; // device: 2 hoff[n_contig] words each
+  uint32_t* start_at = nullptr;
+  ~kma_orf_index() {
+    for (void* p : {(void*)len, (void*)hoff, (void*)stop_at, (void*)start_at})
+      if (p) (void)hipFree(p);
+  }
+};
+
+extern "C" {
+
+int kma_orf_index_create(const uint8_t* dna, const uint64_t* offsets, uint32_t n_contig,
+                         int genetic_code, int device, kma_orf_index** out) {
+  if (!out) return fail(KMA_E_INVALID, "null argument");
+  *out = nullptr;
+  if (!offsets) return fail(KMA_E_INVALID, "null argument");
+  if (genetic_code != 1 && genetic_code != 4 && genetic_code != 11)
+    return fail(KMA_E_INVALID, "genetic code %d: the ORF index knows codes 1, 4 and 11",
+                genetic_code);
+  std::vector<uint64_t> off(n_contig + 1ull), hoff(n_contig + 1ull);
+  std::vector<int32_t> len(n_contig);
+  for (uint32_t c = 0; c < n_contig; ++c) {
+    if (offsets[c + 1] < offsets[c]) return fail(KMA_E_INVALID, "offsets decrease at %u", c);
+    if (offsets[c + 1] - offsets[0] >= (1ull << 31))
+      return fail(KMA_E_INVALID, "2^31 bases or more");
+    off[c + 1] = offsets[c + 1] - offsets[0];
+    len[c] = (int32_t)(offsets[c + 1] - offsets[c]);
+    hoff[c + 1] = hoff[c] + 3ull * kma::orf_frame_slots((uint32_t)len[c]);
+  }
+  const uint64_t total = off[n_contig], half = hoff[n_contig];
+  if (total && !dna) return fail(KMA_E_INVALID, "null argument");
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  std::unique_ptr<kma_orf_index> idx(new kma_orf_index);
+  idx->device = device;
+  idx->n_contig = n_contig;
+  KMA_HIP(hipMalloc(&idx->len, std::max<size_t>(n_contig * 4ull, 4)));
+  KMA_HIP(hipMalloc(&idx->hoff, (n_contig + 1ull) * 8));
+  KMA_HIP(hipMalloc(&idx->stop_at, std::max<size_t>(half * 8, 4)));
+  KMA_HIP(hipMalloc(&idx->start_at, std::max<size_t>(half * 8, 4)));
+  DevBufs b;  // the DNA and the scans' scratch live for the build only
+  DevBatch in;  // (off[] is rebased already; offsets[0] is read only when there are bases)
+  if (int rc = upload_batch(b, total ? dna + offsets[0] : dna, off.data(), n_contig, 0, &in))
+    return rc;
+  kma::OrfBuildArgs a{};
+  a.dna = in.bytes;
+  a.offsets = in.off;
+  a.hoff = idx->hoff;
+  a.n_contig = n_contig;
+  a.half = half;
+  a.stops = genetic_code == 4 ? kma::kOrfStops2 : kma::kOrfStops3;
+  a.stop_at = idx->stop_at;
+  a.start_at = idx->start_at;
+  Scratch tmp;
+  KMA_HIP(kma::launch_orf_build(a, nullptr, tmp.ask(), nullptr));
+  KMA_HIP(tmp.alloc(b));
+  KMA_HIP(hipMemcpy(idx->hoff, hoff.data(), (n_contig + 1ull) * 8, hipMemcpyHostToDevice));
+  if (n_contig) KMA_HIP(hipMemcpy(idx->len, len.data(), n_contig * 4ull, hipMemcpyHostToDevice));
+  KMA_HIP(kma::launch_orf_build(a, tmp.p, tmp.bytes(), nullptr));
+  KMA_HIP(hipStreamSynchronize(nullptr));
+  *out = idx.release();
+  return KMA_OK;
+}
+
+int kma_orf_index_destroy(kma_orf_index* idx) {
+  if (!idx) return KMA_OK;
+  DeviceScope ds(idx->device);
+  delete idx;
+  return KMA_OK;
+}
+
+int kma_extend_proposals(const kma_orf_index* idx, const kma_proposal* props, uint64_t n,
+                         double min_strength, int min_evidence, int32_t* out_left,
+                         int32_t* out_right, uint8_t* out_status, uint64_t* stats) {
+  if (!idx || !stats) return fail(KMA_E_INVALID, "null argument");
+  stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (n == 0) return KMA_OK;
+  if (!props || !out_left || !out_right || !out_status)
+    return fail(KMA_E_INVALID, "null argument");
+  for (uint64_t i = 0; i < n; ++i) {
+    const kma_proposal& p = props[i];
+    if (p.contig >= idx->n_contig)
+      return fail(KMA_E_INVALID, "proposal %llu: contig %u >= %u", (unsigned long long)i,
+                  p.contig, idx->n_contig);
+    if (p.strand != '+' && p.strand != '-')
+      return fail(KMA_E_INVALID, "proposal %llu: strand must be '+' or '-'",
+                  (unsigned long long)i);
+    if ((int64_t)p.right - p.left + 1 < 3)
+      return fail(KMA_E_INVALID, "proposal %llu: shorter than a codon", (unsigned long long)i);
+  }
+  DeviceScope ds(idx->device);
+  if (int rc = ds.entered()) return rc;
+  DevBufs b;
+  kma_proposal* d_props;
+  kma::OrfExtendArgs a{};
+  KMA_HIP(b.alloc(&d_props, n * sizeof(kma_proposal)));
+  KMA_HIP(b.alloc(&a.left, n * 4));
+  KMA_HIP(b.alloc(&a.right, n * 4));
+  KMA_HIP(b.alloc(&a.status, n));
+  KMA_HIP(b.alloc(&a.stats, 32));
+  a.len = idx->len;
+  a.hoff = idx->hoff;
+  a.stop_at = idx->stop_at;
+  a.start_at = idx->start_at;
+  a.props = d_props;
+  a.n = n;
+  a.min_strength = min_strength;
+  a.min_evidence = min_evidence;
+  KMA_HIP(hipMemcpy(d_props, props, n * sizeof(kma_proposal), hipMemcpyHostToDevice));
+  KMA_HIP(hipMemset(a.stats, 0, 32));
+  KMA_HIP(kma::launch_orf_extend(a, nullptr));
+  KMA_HIP(hipMemcpy(stats, a.stats, 32, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_left, a.left, n * 4, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_right, a.right, n * 4, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_status, a.status, n, hipMemcpyDeviceToHost));
+  return KMA_OK;
+}
+
+}  // extern "C"
+
+// ---- protein translation of locations (kma_translate.hip) --------------------------------------
+namespace {
+thread_local double g_translate_kernel_ms = 0.0;  // the last call's kernel (kma_debug_translate_ms)
+}
+
+extern "C" {
+
+int kma_translate_locations(const uint8_t* dna, const uint64_t* offsets, uint32_t n_contig,
+                            int genetic_code, int device, const kma_location* locs,
+                            uint64_t n_loc, int flags, uint8_t* out_residues, uint64_t cap,
+                            uint64_t* out_offsets) {
+  g_translate_kernel_ms = 0.0;
+  if (!offsets || !out_offsets || (n_loc && !locs)) return fail(KMA_E_INVALID, "null argument");
+  if (flags & ~KMA_TR_PEG) return fail(KMA_E_INVALID, "unknown flag bits 0x%x", flags & ~KMA_TR_PEG);
+  const char* code = ncbi_code(genetic_code);
+  if (!code) return fail(KMA_E_INVALID, "genetic code %d is not a known NCBI table", genetic_code);
+  std::vector<uint64_t> off(n_contig + 1ull);
+  for (uint32_t c = 0; c < n_contig; ++c) {
+    if (offsets[c + 1] < offsets[c]) return fail(KMA_E_INVALID, "offsets decrease at %u", c);
+    if (offsets[c + 1] - offsets[0] >= (1ull << 31))
+      return fail(KMA_E_INVALID, "2^31 bases or more");
+    off[c + 1] = offsets[c + 1] - offsets[0];
+  }
+  const int64_t drop = flags & KMA_TR_PEG ? 1 : 0;
+  out_offsets[0] = 0;
+  for (uint64_t i = 0; i < n_loc; ++i) {
+    const kma_location& l = locs[i];
+    const unsigned long long ii = (unsigned long long)i;
+    if (l.contig >= n_contig)
+      return fail(KMA_E_INVALID, "location %llu: contig %u >= %u", ii, l.contig, n_contig);
+    if (l.strand != '+' && l.strand != '-')
+      return fail(KMA_E_INVALID, "location %llu: strand must be '+' or '-'", ii);
+    const int64_t n = (int64_t)(off[l.contig + 1] - off[l.contig]);
+    if (l.left < 1) return fail(KMA_E_INVALID, "location %llu: left %d < 1", ii, l.left);
+    if (l.right > n)
+      return fail(KMA_E_INVALID, "location %llu: right %d past the contig's %lld bases", ii,
+                  l.right, (long long)n);
+    if ((int64_t)l.right < (int64_t)l.left - 1)
+      return fail(KMA_E_INVALID, "location %llu: right %d < left %d - 1", ii, l.right, l.left);
+    const int64_t codons = ((int64_t)l.right - l.left + 1) / 3 - drop;
+    out_offsets[i + 1] = out_offsets[i] + (uint64_t)(codons > 0 ? codons : 0);
+  }
+  const uint64_t total = out_offsets[n_loc];
+  if (total > cap)
+    return fail(KMA_E_CAPACITY, "%llu residues, capacity %llu", (unsigned long long)total,
+                (unsigned long long)cap);
+  if (total == 0) return KMA_OK;
+  if (!dna || !out_residues) return fail(KMA_E_INVALID, "null argument");
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  DevBufs b;
+  DevBatch in;  // (off[] is rebased already; a residue to write means there are bases)
+  if (int rc = upload_batch(b, dna + offsets[0], off.data(), n_contig, 0, &in)) return rc;
+  uint8_t *d_code, *d_out;
+  uint64_t* d_ooff;
+  kma_location* d_locs;
+  KMA_HIP(b.alloc(&d_locs, n_loc * sizeof(kma_location)));
+  KMA_HIP(b.alloc(&d_ooff, (n_loc + 1) * 8));
+  KMA_HIP(b.alloc(&d_code, 64));
+  KMA_HIP(b.alloc(&d_out, total));
+  KMA_HIP(hipMemcpy(d_locs, locs, n_loc * sizeof(kma_location), hipMemcpyHostToDevice));
+  KMA_HIP(hipMemcpy(d_ooff, out_offsets, (n_loc + 1) * 8, hipMemcpyHostToDevice));
+  KMA_HIP(hipMemcpy(d_code, code, 64, hipMemcpyHostToDevice));
+  kma::TranslateArgs a{};
+  a.dna = in.bytes;
+  a.offsets = in.off;
+  a.locs = d_locs;
+  a.out_off = d_ooff;
+  a.n_loc = n_loc;
+  a.total = total;
+  a.code = d_code;
+  a.peg = (uint32_t)(flags & KMA_TR_PEG);
+  a.out = d_out;
+  struct Events {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  KMA_HIP(hipEventCreate(&ev.e[0]));
+  KMA_HIP(hipEventCreate(&ev.e[1]));
+  KMA_HIP(hipEventRecord(ev.e[0], nullptr));
+  KMA_HIP(kma::launch_translate(a, nullptr));
+  KMA_HIP(hipEventRecord(ev.e[1], nullptr));
+  KMA_HIP(hipMemcpy(out_residues, d_out, total, hipMemcpyDeviceToHost));
+  float ms = 0.f;
+  KMA_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  g_translate_kernel_ms = ms;
+  return KMA_OK;
+}
+
+// Not in kmeranno.h: measurement hook. hipEvent time of the kernel of this thread's last
+// kma_translate_locations call (0 when it launched none).
+double kma_debug_translate_ms(void) { return g_translate_kernel_ms; }
+
+}  // extern "C"
+
+namespace {
+// Window keys, per-protein sort and distinct sizes of a batch (device buffers in b): the
+// ProteinKmers sets of kma_hash_annotate's two sides.
+struct KmerSets {
+  uint8_t* res = nullptr;
+  uint64_t* off = nullptr;
+  uint64_t *keys = nullptr, *sorted = nullptr;
+  uint32_t *size = nullptr, *owner = nullptr;
+  uint8_t* first = nullptr;
+  uint64_t total = 0;
+};
+
+int kmer_sets(DevBufs& b, const uint8_t* residues, const uint64_t* offsets, uint32_t n, int k,
+              uint32_t* d_alpha, KmerSets& ks) {
+  DevBatch in;
+  if (int rc = upload_batch(b, residues, offsets, n, 64, &in)) return rc;
+  ks.res = in.bytes, ks.off = in.off, ks.total = in.total;
+  const uint64_t nw = std::max<uint64_t>(ks.total, 1);
+  KMA_HIP(b.alloc(&ks.keys, nw * 8));
+  KMA_HIP(b.alloc(&ks.sorted, nw * 8));
+  KMA_HIP(b.alloc(&ks.size, std::max<uint64_t>(n, 1) * 4));
+  KMA_HIP(b.alloc(&ks.owner, nw * 4));
+  KMA_HIP(b.alloc(&ks.first, nw));
+  KMA_HIP(kma::launch_window_keys(ks.res, ks.off, n, k, 0, ks.keys, d_alpha, nullptr));
+  Scratch tmp;
+  KMA_HIP(kma::launch_segmented_sort(nullptr, tmp.ask(), ks.keys, ks.sorted, ks.total, n, ks.off,
+                                     ks.off + 1, 5 * k, nullptr));
+  KMA_HIP(tmp.alloc(b));
+  KMA_HIP(kma::launch_segmented_sort(tmp.p, tmp.bytes(), ks.keys, ks.sorted, ks.total, n, ks.off,
+                                     ks.off + 1, 5 * k, nullptr));
+  KMA_HIP(kma::launch_distinct(ks.sorted, ks.off, n, ks.size, nullptr));
+  KMA_HIP(kma::launch_owner_first(ks.sorted, ks.off, n, ks.owner, ks.first, nullptr));
+  return KMA_OK;
+}
+
+// One side of kma_hash_annotate (`what` names it in the messages).
+int check_side(const uint8_t* residues, const uint64_t* offsets, uint32_t n, const char* what) {
+  if (n && (!residues || !offsets)) return fail(KMA_E_INVALID, "null %s", what);
+  const std::string too_long = std::string("more than 2^31 ") + what + " residues";
+  return check_offsets(offsets, n, what, 1ull << 31, too_long.c_str());
+}
+}  // namespace
+
+extern "C" {
+
+int kma_hash_annotate(const uint8_t* gres, const uint64_t* goff, uint32_t n_gp,
+                      const uint8_t* pres, const uint64_t* poff, uint32_t n_pt, int k,
+                      double min_sim, int device, int32_t* out_best, double* out_sim,
+                      uint32_t* out_count) {
+  if (k < 2 || k > 12) return fail(KMA_E_INVALID, "kmer size %d outside 2..12", k);
+  if (!(min_sim >= 0.0 && min_sim < 1.0))
+    return fail(KMA_E_INVALID, "Minimum similarity score must be between 0 and 1.");
+  if ((n_gp && (!out_best || !out_sim)) || (n_pt && !out_count))
+    return fail(KMA_E_INVALID, "null output");
+  if (int rc = check_side(gres, goff, n_gp, "genome protein")) return rc;
+  if (int rc = check_side(pres, poff, n_pt, "prototype")) return rc;
+  for (uint32_t i = 0; i < n_gp; ++i) {
+    out_best[i] = -1;
+    out_sim[i] = 0.0;
+  }
+  if (n_pt) std::memset(out_count, 0, n_pt * 4ull);
+  if (n_gp == 0 || n_pt == 0) return KMA_OK;
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  DevBufs b;
+  AlphabetFlag alpha;
+  uint64_t* d_n;  // [0] genome pairs, [1] unique keys, [2] runs
+  if (int rc = alpha.init(b)) return rc;
+  KMA_HIP(b.alloc(&d_n, 32));
+  KMA_HIP(hipMemset(d_n, 0, 32));
+  KmerSets g, p;
+  if (int rc = kmer_sets(b, gres, goff, n_gp, k, alpha.d, g)) return rc;
+  if (int rc = kmer_sets(b, pres, poff, n_pt, k, alpha.d, p)) return rc;
+  if (int rc = alpha.check()) return rc;
+  const int kb = 5 * k;
+  // genome (key, protein) pairs of distinct keys, sorted by key; unique keys and ranges
+  const uint64_t gw = std::max<uint64_t>(g.total, 1);
+  uint64_t *gpk, *skey, *ukeys;
+  uint32_t *gpp, *sprot, *uidx, *ustart;
+  uint8_t* uhead;
+  for (uint64_t** q : {&gpk, &skey, &ukeys}) KMA_HIP(b.alloc(q, gw * 8));
+  for (uint32_t** q : {&gpp, &sprot, &uidx}) KMA_HIP(b.alloc(q, gw * 4));
+  KMA_HIP(b.alloc(&ustart, (gw + 1) * 4));
+  KMA_HIP(b.alloc(&uhead, gw));
+  Scratch t1;
+  KMA_HIP(kma::prim_select_flagged_u64(nullptr, t1.ask(), g.sorted, g.first, gpk, d_n, g.total, nullptr));
+  KMA_HIP(kma::prim_select_flagged_u32(nullptr, t1.ask(), g.owner, g.first, gpp, d_n, g.total, nullptr));
+  KMA_HIP(kma::prim_sort_pairs_u64_u32(nullptr, t1.ask(), gpk, skey, gpp, sprot, g.total, kb, nullptr));
+  KMA_HIP(kma::prim_excl_sum_u32_u64(nullptr, t1.ask(), nullptr, nullptr, std::max<uint64_t>(p.total, 1), nullptr));
+  KMA_HIP(t1.alloc(b));
+  KMA_HIP(kma::prim_select_flagged_u64(t1.p, t1.bytes(), g.sorted, g.first, gpk, d_n, g.total, nullptr));
+  KMA_HIP(kma::prim_select_flagged_u32(t1.p, t1.bytes(), g.owner, g.first, gpp, d_n, g.total, nullptr));
+  uint64_t n_pairs = 0;
+  KMA_HIP(hipMemcpy(&n_pairs, d_n, 8, hipMemcpyDeviceToHost));
+  KMA_HIP(kma::prim_sort_pairs_u64_u32(t1.p, t1.bytes(), gpk, skey, gpp, sprot, n_pairs, kb, nullptr));
+  KMA_HIP(kma::launch_run_heads(skey, n_pairs, uhead, uidx, nullptr));
+  KMA_HIP(kma::prim_select_flagged_u64(t1.p, t1.bytes(), skey, uhead, ukeys, d_n + 1, n_pairs, nullptr));
+  KMA_HIP(kma::prim_select_flagged_u32(t1.p, t1.bytes(), uidx, uhead, ustart, d_n + 1, n_pairs, nullptr));
+  KMA_HIP(kma::launch_set_end(ustart, d_n + 1, n_pairs, nullptr));
+  // candidates: one (prototype, protein) per shared distinct key
+  kma::HashArgs a{};
+  a.n_ppos = p.total;
+  a.pfirst = p.first;
+  a.psorted = p.sorted;
+  a.powner = p.owner;
+  a.psize = p.size;
+  a.ukeys = ukeys;
+  a.n_u = d_n + 1;
+  a.ustart = ustart;
+  a.gprot = sprot;
+  a.gsize = g.size;
+  a.min_sim = min_sim;
+  const uint64_t pw = std::max<uint64_t>(p.total, 1);
+  uint64_t* coff;
+  KMA_HIP(b.alloc(&a.ccount, pw * 4));
+  KMA_HIP(b.alloc(&a.cu, pw * 4));
+  KMA_HIP(b.alloc(&coff, pw * 8));
+  a.coff = coff;
+  KMA_HIP(kma::launch_cand_count(a, nullptr));
+  KMA_HIP(kma::prim_excl_sum_u32_u64(t1.p, t1.bytes(), a.ccount, coff, p.total, nullptr));
+  uint64_t last_off = 0;
+  uint32_t last_cnt = 0;
+  if (p.total) {
+    KMA_HIP(hipMemcpy(&last_off, coff + p.total - 1, 8, hipMemcpyDeviceToHost));
+    KMA_HIP(hipMemcpy(&last_cnt, a.ccount + p.total - 1, 4, hipMemcpyDeviceToHost));
+  }
+  const uint64_t n_cand = last_off + last_cnt;
+  KMA_HIP(b.alloc(&a.out_count, n_pt * 4ull));
+  uint64_t* best_bits;
+  uint32_t* best_proto;
+  KMA_HIP(b.alloc(&best_bits, n_gp * 8ull));
+  KMA_HIP(b.alloc(&best_proto, n_gp * 4ull));
+  KMA_HIP(b.alloc(&a.best_bits, n_gp * 8ull));
+  KMA_HIP(b.alloc(&a.best_proto, n_gp * 4ull));
+  KMA_HIP(hipMemset(a.out_count, 0, n_pt * 4ull));
+  for (uint64_t* q : {best_bits, a.best_bits}) KMA_HIP(hipMemset(q, 0, n_gp * 8ull));
+  for (uint32_t* q : {best_proto, a.best_proto}) KMA_HIP(hipMemset(q, 0xFF, n_gp * 4ull));
+  // Candidates are scored in slices of whole prototypes (file order) whose sort and run-length
+  // encoding stay below 2^31 elements (the int counts of the CUB-style APIs this was first written against; rocPRIM's select and sort take size_t, its run-length encode still unsigned); a slice's best per protein
+  // replaces the running best only when strictly higher, so earlier prototypes keep ties.
+  // KMA_OPT_HASH_SLICE (tests) lowers the slice size.
+  uint64_t slice_cap = (1ull << 31) - 1;
+  if (const int64_t o = opt(KMA_OPT_HASH_SLICE); o > 0)
+    slice_cap = std::min<uint64_t>(slice_cap, (uint64_t)o);
+  std::vector<uint64_t> cum(n_pt + 1, 0);
+  if (n_cand) {
+    uint64_t* d_cum;
+    KMA_HIP(b.alloc(&d_cum, (n_pt + 1) * 8ull));
+    KMA_HIP(kma::launch_proto_cum(coff, a.ccount, p.off, n_pt, p.total, d_cum, nullptr));
+    KMA_HIP(hipMemcpy(cum.data(), d_cum, (n_pt + 1) * 8ull, hipMemcpyDeviceToHost));
+  }
+  std::vector<uint32_t> cut{0};  // slice boundaries in prototypes
+  for (uint32_t q = 0; q < n_pt; ++q) {
+    if (cum[q + 1] - cum[q] > (1ull << 31) - 1)
+      return fail(KMA_E_CAPACITY, "prototype %u has %llu candidates (limit 2^31 - 1)", q,
+                  (unsigned long long)(cum[q + 1] - cum[q]));
+    if (q > cut.back() && cum[q + 1] - cum[cut.back()] > slice_cap) cut.push_back(q);
+  }
+  cut.push_back(n_pt);
+  uint64_t max_slice = 0;
+  for (size_t i = 0; i + 1 < cut.size(); ++i)
+    max_slice = std::max(max_slice, cum[cut[i + 1]] - cum[cut[i]]);
+  if (max_slice) {
+    uint64_t *cand, *csorted, *runs;
+    uint32_t* run_len;
+    KMA_HIP(b.alloc(&cand, max_slice * 8));
+    KMA_HIP(b.alloc(&csorted, max_slice * 8));
+    KMA_HIP(b.alloc(&runs, max_slice * 8));
+    KMA_HIP(b.alloc(&run_len, max_slice * 4));
+    int pbits = 1;
+    while (pbits < 32 && (1ull << pbits) < n_pt) ++pbits;
+    Scratch t2;
+    KMA_HIP(kma::prim_sort_keys_u64(nullptr, t2.ask(), cand, csorted, max_slice, 32 + pbits, nullptr));
+    KMA_HIP(kma::prim_rle_u64(nullptr, t2.ask(), csorted, runs, run_len, d_n + 2, max_slice, nullptr));
+    KMA_HIP(t2.alloc(b));
+    std::vector<uint64_t> hoff(n_pt + 1);
+    KMA_HIP(hipMemcpy(hoff.data(), p.off, (n_pt + 1) * 8ull, hipMemcpyDeviceToHost));
+    a.cand = cand;
+    a.runs = runs;
+    a.run_len = run_len;
+    a.n_runs = d_n + 2;
+    for (size_t i = 0; i + 1 < cut.size(); ++i) {
+      const uint64_t nc = cum[cut[i + 1]] - cum[cut[i]];
+      if (!nc) continue;
+      a.pos_lo = hoff[cut[i]] - hoff[0];
+      a.pos_hi = hoff[cut[i + 1]] - hoff[0];
+      a.cand_base = cum[cut[i]];
+      KMA_HIP(kma::launch_cand_emit(a, nullptr));
+      KMA_HIP(kma::prim_sort_keys_u64(t2.p, t2.bytes(), cand, csorted, nc, 32 + pbits, nullptr));
+      KMA_HIP(kma::prim_rle_u64(t2.p, t2.bytes(), csorted, runs, run_len, d_n + 2, nc, nullptr));
+      KMA_HIP(kma::launch_score(a, nc, nullptr));
+      KMA_HIP(kma::launch_choose(a, nc, nullptr));
+      KMA_HIP(kma::launch_merge_best(best_bits, best_proto, a.best_bits, a.best_proto, n_gp,
+                                     nullptr));
+    }
+  }
+  std::vector<uint64_t> bits(n_gp);
+  std::vector<uint32_t> proto(n_gp);
+  KMA_HIP(hipMemcpy(bits.data(), best_bits, n_gp * 8ull, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(proto.data(), best_proto, n_gp * 4ull, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_count, a.out_count, n_pt * 4ull, hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < n_gp; ++i) {
+    if (proto[i] == 0xFFFFFFFFu) continue;
+    std::memcpy(&out_sim[i], &bits[i], 8);
+    out_best[i] = (int32_t)proto[i];
+  }
+  return KMA_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // kma_distance.h — launchers of the ProteinKmers.distance kernels (kma_distance.hip), used by
-// kma_abi.cpp. Not part of the public ABI (see include/kmeranno.h).
+// kma_abi_ops.cpp. Not part of the public ABI (see include/kmeranno.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // kma_hashanno.h — launchers of the hash annotator's scoring kernels (kma_hashanno.hip), used by
-// kma_abi.cpp. Not part of the public ABI (see include/kmeranno.h).
+// kma_abi_ops.cpp. Not part of the public ABI (see include/kmeranno.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

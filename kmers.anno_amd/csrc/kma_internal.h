@@ -1,5 +1,5 @@
 // kma_internal.h — shared between the HIP kernels (kma_kernels.hip) and the C-ABI layer
-// (kma_abi.cpp). Not part of the public ABI (see include/kmeranno.h).
+// (kma_abi_*.cpp). Not part of the public ABI (see include/kmeranno.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -171,7 +171,7 @@ __host__ __device__ inline uint32_t mmer_hash(uint32_t sub) {
 //          began as a size rule (tables beyond the Infinity Cache); with t = 1 and the cheaper
 //          bucket match the 10^7 table measures c4 2.284 vs 2.763 ms, c2 -2%, c3 even
 //          (profiles/r06/order_small_tables_r06j/), and every K = 8, m = 6 table takes it
-//          (kma_abi.cpp minimizer_len). Not kept: the open-closed t = 3 variant (3-mers whose middle residue code is
+//          (kma_abi_table.cpp minimizer_len). Not kept: the open-closed t = 3 variant (3-mers whose middle residue code is
 //          below both neighbours' rank first; simulated density 0.410) at 3.03 ms against
 //          2.88, its VALU per window costing more than the fewer home lines save; t = 2 and 4
 //          simulate at 0.467 / 0.468.
@@ -334,12 +334,12 @@ constexpr double kMaxDisplacedTwoChoice = 0.40;
 // 1 - 2/(K - m + 2): 1/2 for m = 6, 1/3 for m = 7. The size rule: m = 6 up to
 // kMinimizer6Buckets buckets (134M keys at load factor 0.5), else 7 (m <= K); KMA_MINIMIZER=
 // 0|6|7 in the environment forces a layout (read per call: tests run every layout in one
-// process). Defined in kma_abi.cpp.
+// process). Defined in kma_abi_table.cpp.
 constexpr uint64_t kMinimizer6Buckets = kSlotsPerBucket == 16 ? (1ull << 24) : (1ull << 25);
 // Wide tables (4 slots per bucket): the same key count, i.e. twice the buckets.
 constexpr uint64_t kMinimizer6BucketsWide = 1ull << 26;
 int minimizer_len(int k, uint64_t n_buckets);
-// The creators then measure the table they built (kma_abi.cpp create_from_device_keys): every
+// The creators then measure the table they built (kma_abi_table.cpp create_from_device_keys): every
 // displaced key costs a dependent round trip when it is looked up, and false filter hits cost
 // the misses the same. Measured at c5 (10^8 keys, paired homes, hashed chains; round 3 sweep,
 // profiles/r03_layout/): m = 6 / m = 7 / flat take 4.12 / 4.11 / 5.57 ms at load factor 0.5

@@ -1,4 +1,4 @@
-// kma_orf.h — the projector's ORF index (kma_orf.hip) shared with the C-ABI layer (kma_abi.cpp).
+// kma_orf.h — the projector's ORF index (kma_orf.hip) shared with the C-ABI layer (kma_abi_ops.cpp).
 // Not part of the public ABI (see include/kmeranno.h, kma_orf_index_create / kma_extend_proposals).
 //
 // Layout. A contig of n bases has cnt = ceil(n / 3) slots per (strand, frame): slot (s, f, j)

@@ -147,7 +147,7 @@ unsigned grid_of(uint64_t n) {
 }  // namespace
 
 // The whole sweep on `stream`; a.stats (4 u64) must be zeroed before. Scratch sizes: see
-// kma_abi.cpp (kma_propose_pegs). temp == nullptr: *temp_bytes = the sort / scan scratch.
+// kma_abi_ops.cpp (kma_propose_pegs). temp == nullptr: *temp_bytes = the sort / scan scratch.
 hipError_t launch_propose(PropArgs a, void* temp, size_t* temp_bytes, hipStream_t stream) {
   const size_t n = a.n;
   const rocprim::plus<uint32_t> add;

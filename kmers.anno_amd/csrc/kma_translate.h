@@ -1,5 +1,5 @@
 // kma_translate.h — protein translation of genome locations (kma_translate.hip) shared with the
-// C-ABI layer (kma_abi.cpp). Not part of the public ABI (see include/kmeranno.h,
+// C-ABI layer (kma_abi_ops.cpp). Not part of the public ABI (see include/kmeranno.h,
 // kma_translate_locations).
 //
 // Residue r of the flat output belongs to the location i with out_off[i] <= r < out_off[i + 1]

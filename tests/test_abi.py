@@ -58,8 +58,12 @@ def test_options_set_get_validate_restore(native_lib):
     assert [k.get_option(o) for o in range(1, 11)] == [-1, 0, -1, 0, 0, 1, 0, 0, -1, 0]
     assert k.layout_for(8, 1000) == 6 | k.LAYOUT_MOD_SAMPLING | k.LAYOUT_TWO_CHOICE
     assert k.layout_for(7, 1000) == 6 | k.LAYOUT_TWO_CHOICE
-    src = open(os.path.join(ROOT, "kmers.anno_amd", "csrc", "kma_abi.cpp")).read()
-    assert src.count("getenv(") == 1 and "#if KMA_TUNING_ENV" in src
+    csrc = os.path.join(ROOT, "kmers.anno_amd", "csrc")
+    host = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))
+            if f.endswith((".cpp", ".h"))}
+    reads_env = [f for f, src in host.items() if "getenv(" in src]
+    assert len(reads_env) == 1 and host[reads_env[0]].count("getenv(") == 1
+    assert "#if KMA_TUNING_ENV" in host[reads_env[0]]
 
 
 def test_bucket_sizing_host_helper(native_lib):
@@ -121,7 +125,7 @@ def test_table_layout_host_helper(native_lib, monkeypatch):
 
 
 def test_choose_layout_rule():
-    """kmeranno.choose_layout mirrors the creators' rule (kma_abi.cpp create_from_device_keys).
+    """kmeranno.choose_layout mirrors the creators' rule (kma_abi_table.cpp create_from_device_keys).
     Two-choice placement first: kept when it builds (the size rule's m), rebuilt flat when more
     than 40% of the keys are outside their home and flat halves them; a minimizer build that fails
     is retried flat. A failed two-choice build falls back to the chained rule, shown on the round-3 c5 sweep's build statistics {full,

@@ -115,7 +115,7 @@ def test_config5_size_sample_and_properties(kma, oracle_c, c5data, monkeypatch):
 @pytest.mark.timeout(600)
 def test_config5_load_factor_09(kma, oracle_c, c5data, monkeypatch):
     """c5 at load factor 0.9 (10^8 keys in 1.39e7 buckets: long overflow chains): the table
-    the creator keeps (its layout rule, kma_abi.cpp create_from_device_keys) answers a 20k
+    the creator keeps (its layout rule, kma_abi_table.cpp create_from_device_keys) answers a 20k
     sample bit-exactly and the whole batch exactly like the LF 0.5 table and like the 0.9
     tables of the other layouts."""
     sig, res, off, _, _ = c5data

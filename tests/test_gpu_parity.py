@@ -457,7 +457,7 @@ def test_config2_size_vs_oracle(kma, oracle_c, path, monkeypatch):
          "ascii-5pieces"])
 def test_host_call_pipelined_pieces_vs_oracle(kma, oracle_c, opts, pieces):
     """A host call of ~48M residues runs as 2-16 pieces whose H2D overlaps the previous
-    piece's kernel (kma_abi.cpp protein_shard): packed input streamed out in segments as the
+    piece's kernel (kma_abi_proteins.cpp protein_shard): packed input streamed out in segments as the
     staging pool packs it (the calling thread alone with one staging thread), ASCII input piece
     by piece (uneven pieces, weights 1, 2, 4, ..., 4, 2, 1, at 4 pieces and more): every protein,
     including those next to piece and segment boundaries, and the tally (summed over the pieces'
