@@ -3,7 +3,7 @@
 // per-table pool of host contexts (kma_objects.h) the host entry points draw from.
 //
 // Host-side orchestration only: argument checks, key packing, device allocation and copies,
-// replica management and kernel launches (kma_kernels.hip). No compute falls back to the CPU:
+// replica management and kernel launches (kma_build.hip). No compute falls back to the CPU:
 // without a usable HIP device every entry point that needs one returns KMA_E_DEVICE.
 #include <chrono>
 
@@ -230,7 +230,7 @@ int build_on_device(uint64_t* d_slots, uint64_t n_buckets, int k, int m, uint32_
   return KMA_OK;
 }
 
-// Two-choice build (kma_kernels.hip launch_build_two_choice) into zeroed slots on stream s; its
+// Two-choice build (kma_build.hip launch_build_two_choice) into zeroed slots on stream s; its
 // sort buffers are allocated here and freed after the stream has drained them.
 int build_two_choice_on_device(uint64_t* d_slots, uint64_t n_buckets, int k, int m,
                                const uint64_t* d_keys, const uint32_t* d_fids, uint64_t n,
@@ -255,7 +255,7 @@ int build_two_choice_on_device(uint64_t* d_slots, uint64_t n_buckets, int k, int
   KMA_HIP(tmp.alloc(&rows, n * 4));
   KMA_HIP(tmp.alloc(&srows, n * 4));
   KMA_HIP(tmp.alloc(&temp, temp_bytes));
-  KMA_HIP(tmp.alloc(&x.home, n * 4));  // home-first placement (kma_kernels.hip)
+  KMA_HIP(tmp.alloc(&x.home, n * 4));  // home-first placement (kma_build.hip)
   KMA_HIP(tmp.alloc(&x.sorted_home, n * 4));
   KMA_HIP(tmp.alloc(&x.sorted_idx, n * 4));
   KMA_HIP(tmp.alloc(&x.away, n));

@@ -1,5 +1,6 @@
-// kma_device.h — device helpers shared by the probe kernels (kma_kernels.hip): wave reductions, window packing, bucket scans and the quad-cooperative
-// bucket match. Internal; not part of the ABI.
+// kma_device.h — device helpers shared by the kernel units (kma_kernels.hip, kma_contigs.hip,
+// kma_build.hip and the operators' units): wave reductions, window packing, bucket scans and the
+// quad-cooperative bucket match. Internal; not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -189,10 +190,6 @@ template <int R>
 __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, R * 0x55, 0xF, 0xF, false);
 }
-__device__ __forceinline__ uint32_t quad_or(uint32_t v) {
-  v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);  // [1,0,3,2]
-  return v | (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, false);  // [2,3,0,1]
-}
 
 // One quad's verdict on a bucket it loaded cooperatively: lane `part` holds slots 2part and
 // 2part + 1 of each 64-byte half h of the bucket in v[h] (slots 8h + 2part, 8h + 2part + 1)
@@ -236,18 +233,11 @@ __device__ __forceinline__ uint32_t match_part_raw(const uint4 (&v)[kBucketHalve
   if constexpr (2 * FB > 4) missing = (missing | missing >> FB) & ((1u << FB) - 1u);  // <= 4 bits
   return w | missing << kAbsentShift;  // nonzero: a filter position of the key is clear
 }
-__device__ __forceinline__ uint32_t match_part(const uint4 (&v)[kBucketHalves], uint32_t kl,
-                                               uint32_t kh, uint32_t need, uint32_t part) {
-  return quad_or(match_part_raw(v, kl, kh, need, part));
-}
 
 // Reduce-scatter over a quad of the four buckets' lane verdicts a[r] (match_part_raw): lane
 // `part` returns the OR over the quad of a[part], i.e. its own window's verdict, by a two-round
-// butterfly (3 DPP + 3 OR + 6 lane-constant selects) in place of four quad_or and a select per
-// bucket (8 DPP + 8 OR + 4 selects).
-#ifndef KMA_QUAD_XPOSE
-#define KMA_QUAD_XPOSE 1
-#endif
+// butterfly (3 DPP + 3 OR + 6 lane-constant selects) in place of an OR over the quad and a select
+// per bucket (8 DPP + 8 OR + 4 selects).
 __device__ __forceinline__ uint32_t quad_reduce_scatter(const uint32_t (&a)[4], uint32_t part) {
   const bool hi2 = (part & 2u) != 0u, hi1 = (part & 1u) != 0u;
   const uint32_t s0 = hi2 ? a[0] : a[2], s1 = hi2 ? a[1] : a[3];  // the partner's half
@@ -259,7 +249,7 @@ __device__ __forceinline__ uint32_t quad_reduce_scatter(const uint32_t (&a)[4], 
 }
 
 // Wide tables (K > 8, kma_internal.h): lane `part` of the quad holds slot `part` of the bucket
-// in v (and its filter positions 2part .. in .z); same verdict word as match_part.
+// in v (and its filter positions 2part .. in .z); same verdict word as match_part_raw.
 __device__ __forceinline__ uint32_t match_wide_raw(const uint4& v, uint32_t kl, uint32_t kh,
                                                    uint32_t need, uint32_t part) {
   const uint32_t m = (uint32_t)(v.x == kl) & (uint32_t)(v.y == kh);
@@ -311,13 +301,9 @@ constexpr uint32_t kBucketIdx = (1u << kBucketBits) - 1u;
 
 // Set-entry index of `key` in a set of `cap` entries (fast range, any capacity).
 __device__ __forceinline__ uint32_t set_slot(uint32_t key, uint32_t cap) {
-#if KMA_HASH_LITE
   uint32_t h = key * 0x9E3779B1u;
   h ^= h >> 16;
   return (uint32_t)(((uint64_t)h * cap) >> 32);
-#else
-  return (uint32_t)(((uint64_t)mix32(key * 0x9E3779B1u) * cap) >> 32);
-#endif
 }
 
 }  // namespace

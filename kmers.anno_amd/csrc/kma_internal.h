@@ -1,5 +1,5 @@
-// kma_internal.h — shared between the HIP kernels (kma_kernels.hip) and the C-ABI layer
-// (kma_abi_*.cpp). Not part of the public ABI (see include/kmeranno.h).
+// kma_internal.h — shared between the HIP kernel units (kma_kernels.hip, kma_contigs.hip,
+// kma_build.hip and the operators' units) and the C-ABI layer (kma_abi_*.cpp). Not part of the public ABI (see include/kmeranno.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -46,7 +46,7 @@ static_assert(kFilterBits >= 1 && kFilterBits <= 3, "one to three filter bits pe
 constexpr uint32_t kFidBits = 24 - kFilterBits;  // fid width (KMA_MAX_FID: 22 bits)
 constexpr uint32_t kFidMask = (1u << kFidBits) - 1;
 constexpr uint32_t kKeyHiMask = 0xFF000000u;   // key bits 32..39 in the high dword
-// The probe's verdict word (match_part / match_wide): on a match the fid in bits 0..kFidBits-1
+// The probe's verdict word (match_part_raw / match_wide_raw): on a match the fid in bits 0..kFidBits-1
 // and kWordHit (bit kFidBits), the slot in the bucket from bit 24 (kSlotShift), and from bit 28
 // (kAbsentShift) the key's filter positions that are clear in its home bucket (nonzero: the key
 // is not further down the chain). A probed window whose word is 0 missed its home bucket with
@@ -65,30 +65,23 @@ __host__ __device__ inline uint64_t slot_make(uint64_t key, uint32_t fid) {
 // Filter position h (0 .. kFilterBits - 1) of a key in a bucket of S slots (from the key's low
 // dword): position i lives in slot i / kFilterBits, at bit kFidBits + i % kFilterBits of the
 // slot's high dword (narrow) or .z (wide).
-// KMA_HASH_LITE (default 1): the probe's per-window hashes use one 32-bit multiply each where
-// round 3's first build used two to four (the protein and 6-frame probes issue a VALU
-// instruction every ~4 cycles per SIMD: c5 3,107 VALU instructions per wave, profiles/r03q_sq/).
-// Both filter positions come from one product; the minimizer order is a multiplicative hash of
-// the m-mer (a bijection: no ties); the home bucket a one-multiply mix of the minimizer; the
-// paired-home bit the key's parity. c5: 3.84 vs 4.04 ms and 3.99 vs 4.11 ms against the
-// murmur hashes on two boxes, displaced keys 7.58% vs 7.70% (profiles/r03r/, r03s/).
-#ifndef KMA_HASH_LITE
-#define KMA_HASH_LITE 1
-#endif
+// Lite hashes: the probe's per-window hashes use one 32-bit multiply each where round 3's
+// first build used two to four (the protein and 6-frame probes issue a VALU instruction every
+// ~4 cycles per SIMD: c5 3,107 VALU instructions per wave, profiles/r03q_sq/). Both filter
+// positions come from one product; the minimizer order is a multiplicative hash of the m-mer
+// (a bijection: no ties); the home bucket a one-multiply mix of the minimizer; the paired-home
+// bit the key's parity. c5: 3.84 vs 4.04 ms and 3.99 vs 4.11 ms against the murmur hashes on
+// two boxes, displaced keys 7.58% vs 7.70% (profiles/r03r/, r03s/).
 template <int S>
 __host__ __device__ inline uint32_t filter_pos(uint32_t klo, int h) {
   constexpr int n = S * kFilterBits;  // positions per bucket
   constexpr int bits = (n == 32) ? 5 : (n == 16) ? 4 : (n == 8) ? 3 : 2;
-#if KMA_HASH_LITE
   const uint32_t x = klo * 0x9E3779B1u;
   if constexpr ((n & (n - 1)) != 0) {  // 3 bits per slot: 24 (12 wide) positions, fast range
     const uint32_t r = h == 0 ? x : h == 1 ? (x << 11 | x >> 21) : (x << 22 | x >> 10);
     return (uint32_t)(((uint64_t)r * n) >> 32);
   }
   return h ? (x >> (32 - 2 * bits)) & ((1u << bits) - 1u) : x >> (32 - bits);
-#else
-  return ((klo * (h ? 0x85EBCA77u : 0x9E3779B1u)) + (h ? 0x165667B1u : 0u)) >> (32 - bits);
-#endif
 }
 // The key's filter positions as a mask over the bucket's S * kFilterBits positions (computed
 // once per window by its lane and broadcast to the quad that probes it).
@@ -141,11 +134,7 @@ __host__ __device__ inline uint32_t parity32(uint32_t x) {
 // Minimizer of a packed K-mer: the smallest hash over its K - m + 1 m-mers (5-bit residue
 // codes, first residue most significant). m is a table property (minimizer_len below).
 __host__ __device__ inline uint32_t mmer_hash(uint32_t sub) {
-#if KMA_HASH_LITE
   return sub * 0x9E3779B1u;
-#else
-  return mix32(sub * 0x9E3779B1u + 0x7F4A7C15u);
-#endif
 }
 // Minimizer ORDER (round 6; a table property, a bit of the layout code and of the kernels' M):
 // how a key picks the m-mer its home is a hash of. Consecutive windows of a protein share their
@@ -234,22 +223,14 @@ __host__ __device__ inline uint32_t home_from_hash(uint32_t h, uint64_t key, int
                                                    uint32_t n_buckets) {
   if (m != 0 && n_buckets >= 2) {
     const uint32_t pair = (uint32_t)(((uint64_t)h * (n_buckets >> 1)) >> 32);
-#if KMA_HASH_LITE
     return 2u * pair + parity32((uint32_t)key);
-#else
-    return 2u * pair + (((uint32_t)key * 0x2C1B3C6Du) >> 31);
-#endif
   }
   return (uint32_t)(((uint64_t)h * n_buckets) >> 32);
 }
 // The home of a key (minimizer layouts) from its minimizer hash.
 __host__ __device__ inline uint32_t home_from_min(uint32_t mn, uint64_t key, int m,
                                                   uint32_t n_buckets) {
-#if KMA_HASH_LITE
   return home_from_hash(mix32_lite(mn ^ 0x85EBCA77u), key, m, n_buckets);
-#else
-  return home_from_hash(mix32(mn ^ 0x85EBCA77u), key, m, n_buckets);
-#endif
 }
 __host__ __device__ inline uint32_t home_bucket(uint64_t key, int k, int m, uint32_t n_buckets) {
   if (m == 0)
@@ -378,12 +359,9 @@ constexpr uint32_t kMaxChain = 32;
 constexpr int kProbeWin = KMA_PROBE_WIN;
 constexpr int kBlockProteins = KMA_BLOCK_PROTEINS;
 constexpr int kSetPool = KMA_SET_POOL;
-// Lane permutation of the probe loops (kma_kernels.hip): one load instruction covers 16
-// consecutive windows, so windows sharing a minimizer share a line inside the instruction.
-// c5 3.96 vs 4.03 ms (profiles/r03_ab/).
-#ifndef KMA_LANE_PERM
-#define KMA_LANE_PERM 1
-#endif
+// Lane permutation of the probe loops (kma_kernels.hip chunk_window, kma_contigs.hip): one load
+// instruction covers 16 consecutive windows, so windows sharing a minimizer share a line inside
+// the instruction. Measured c5 3.96 vs 4.03 ms against position order (profiles/r03_ab/).
 #ifndef KMA_CHAIN_Q
 #define KMA_CHAIN_Q 192
 #endif
@@ -511,7 +489,7 @@ constexpr int kContigTile = 256 * kContigPos * kContigSeq;  // forward positions
 // probe 0.0789 vs 0.0745 ms (profiles/r05/c3_stream_ab_r05e.log); codes ORed into the streams
 // by the translation pass (LDS atomics), 0.0766 vs 0.0748 ms (c3_stream_ab_r05f.log). The VALU
 // saved was not on the probe's critical path, the per-block phases were (the variant is in the
-// history of kma_kernels.hip).
+// history of kma_kernels.hip, where the 6-frame probe lived before kma_contigs.hip).
 // A persistent 6-frame grid (one resident wave of blocks striding over the tiles, each block
 // loading its next tile's DNA under the current tile's probes) was also built in round 5 and
 // measured slower: probe 0.0796-0.0803 vs 0.0772-0.0773 ms for a block per tile, ABAB on one
@@ -544,7 +522,7 @@ struct PropArgs {
 };
 hipError_t launch_propose(PropArgs a, void* temp, size_t* temp_bytes, hipStream_t stream);
 
-// ---- launchers (kma_kernels.hip) --------------------------------------------------------------
+// ---- launchers: table build and sort-and-scan builders (kma_build.hip) -------------------------
 // status[0] = table full; stats (finalize) = {entries, max chain, displaced keys}.
 hipError_t launch_build_insert(uint64_t* slots, uint32_t* winner, uint32_t n_buckets, int k,
                                int m, const uint64_t* keys, uint64_t n, uint32_t* status,
@@ -571,15 +549,6 @@ hipError_t launch_build_two_choice(uint64_t* slots, uint32_t n_buckets, int k, i
                                    uint64_t* sorted_keys, uint32_t* rows, uint32_t* sorted_rows,
                                    const TwoChoiceScratch& x, void* temp, size_t* temp_bytes,
                                    uint32_t* status, hipStream_t stream);
-hipError_t launch_annotate(const ProteinArgs& a, hipStream_t stream);  // the protein path
-// ASCII residues [offsets[0], offsets[0] + n) -> the packed stream (packed_bytes(n) bytes; the
-// LUT of the table's replica): pack_residues_kernel.
-hipError_t launch_pack_residues(const uint8_t* residues, const uint64_t* offsets, uint64_t n,
-                                const uint8_t* lut, uint8_t* out, hipStream_t stream);
-// Bytes of the packed stream of n residues: 40 per 64 residues and 16 of read padding.
-__host__ __device__ constexpr uint64_t packed_bytes(uint64_t n) { return 40 * ((n + 63) / 64) + 16; }
-hipError_t launch_contigs_emit(const ContigArgs& a, uint64_t n_blocks, hipStream_t stream);
-hipError_t launch_contigs_probe(const ContigArgs& a, uint64_t n_blocks, hipStream_t stream);
 // Peg-kmer singleton table (KmerReference.countPegKmers + CountMap.getSingletons): every
 // window i < L-K without 'X' of every peg -> (key or 0, peg index) per residue position; sort;
 // keep keys that occur exactly once.
@@ -607,5 +576,18 @@ hipError_t launch_select_flagged(void* temp, size_t* temp_bytes, const uint64_t*
                                  const uint32_t* vals_in, const uint8_t* flags, uint64_t* keys_out,
                                  uint32_t* vals_out, uint64_t* n_out, uint64_t n,
                                  hipStream_t stream);
+
+// ---- launchers: protein probe (kma_kernels.hip) ------------------------------------------------
+hipError_t launch_annotate(const ProteinArgs& a, hipStream_t stream);  // the protein path
+// ASCII residues [offsets[0], offsets[0] + n) -> the packed stream (packed_bytes(n) bytes; the
+// LUT of the table's replica): pack_residues_kernel.
+hipError_t launch_pack_residues(const uint8_t* residues, const uint64_t* offsets, uint64_t n,
+                                const uint8_t* lut, uint8_t* out, hipStream_t stream);
+// Bytes of the packed stream of n residues: 40 per 64 residues and 16 of read padding.
+__host__ __device__ constexpr uint64_t packed_bytes(uint64_t n) { return 40 * ((n + 63) / 64) + 16; }
+
+// ---- launchers: 6-frame path (kma_contigs.hip) -------------------------------------------------
+hipError_t launch_contigs_probe(const ContigArgs& a, uint64_t n_blocks, hipStream_t stream);
+hipError_t launch_contigs_emit(const ContigArgs& a, uint64_t n_blocks, hipStream_t stream);
 
 }  // namespace kma

@@ -43,8 +43,9 @@ def contigs_timeline():
                                          d_nh.data_ptr(), 0, 0, sp)
     torch.cuda.synchronize()
     lib = C.CDLL(os.environ["KMERANNO_LIB"])
-    full = np.zeros(8 * 65536, np.uint64)
-    assert lib.kma_debug_block_clock(full.ctypes.data_as(C.c_void_p), C.c_uint64(8 * 65536)) == 0
+    full = np.zeros(8 * 65536, np.uint64)  # (the 6-frame unit's own buffer and reader)
+    assert lib.kma_debug_block_clock_contigs(full.ctypes.data_as(C.c_void_p),
+                                             C.c_uint64(8 * 65536)) == 0
     rows = full.reshape(65536, 8)
     nb = int((rows[:, 0] != 0).sum())  # blocks of the last launch (tile size from the build)
     clk = rows[:nb][:, :6].astype(np.int64)

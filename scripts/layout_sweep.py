@@ -129,7 +129,7 @@ def main():
 
 def adversarial_workload():
     """~1.5M keys built to share 2,000 minimizers and 200k proteins assembled from them: the
-    cores are the 2,000 6-mers of lowest m-mer hash (kma_internal.h mmer_hash, KMA_HASH_LITE:
+    cores are the 2,000 6-mers of lowest m-mer hash (kma_internal.h mmer_hash:
     the 32-bit product with 0x9E3779B1) among 2M random ones, so every key built around one has
     it as its minimizer at m = 6."""
     rng = np.random.default_rng(23)

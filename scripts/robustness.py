@@ -100,7 +100,7 @@ def main():
     packed = np.zeros(len(cand), np.uint64)
     for j in range(6):
         packed = (packed << np.uint64(5)) | (cand[:, j].astype(np.uint64) - np.uint64(64))
-    # the shipped m-mer order (kma_internal.h mmer_hash, KMA_HASH_LITE): one 32-bit multiply
+    # the shipped m-mer order (kma_internal.h mmer_hash): one 32-bit multiply
     h = (packed * np.uint64(0x9E3779B1)) & np.uint64(0xFFFFFFFF)
     cores = cand[np.argsort(h)[:2000]]
     codes = np.arange(1, 21, dtype=np.uint64)[rng.integers(0, 20, (2000, 3, 400, 2))]

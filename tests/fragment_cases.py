@@ -25,7 +25,7 @@ from test_gpu_translate import STAMP, close_genome, java_4f, raw_and_peg  # noqa
 
 K = 8
 CONTIG_TILE = 1024  # forward positions per 6-frame probe block: kContigTile (csrc/kma_internal.h)
-OFF_CACHE = 64      # offsets a probe block caches: kOffCache (csrc/kma_kernels.hip)
+OFF_CACHE = 64      # offsets a probe block caches: kOffCache (csrc/kma_contigs.hip)
 TR_TILE = 1024      # residues per translate block: kTrTile (csrc/kma_translate.h)
 BOUNDARY_COUNTS = (63, 64, 65, 4095, 4096, 4097)
 PAST = (0, 1, 3 * K - 1, 3 * K, 3 * K + 2)  # a contig's last base, in bases past a tile boundary

@@ -326,7 +326,7 @@ def test_adversarial_minimizer_keys_fall_back_flat(kma, oracle_c, path):
     packed = np.zeros(len(cand), np.uint64)
     for j in range(6):
         packed = (packed << np.uint64(5)) | (cand[:, j].astype(np.uint64) - np.uint64(64))
-    # the minimizer order of kma_internal.h (KMA_HASH_LITE: a multiplicative hash of the 6-mer)
+    # the minimizer order of kma_internal.h (mmer_hash: a multiplicative hash of the 6-mer)
     h = (packed * np.uint64(0x9E3779B1)) & np.uint64(0xFFFFFFFF)
     cores = [cand[i].tobytes().decode() for i in np.argsort(h)[:40]]
     keys = set()
