@@ -315,10 +315,11 @@ int kma_table_device_ptr(const kma_table* table, void** d_slots, uint64_t* bytes
 
 /* ---- workspaces -----------------------------------------------------------------------------
  * Per-stream scratch of the _device entry points. kma_workspace_reserve_batch sizes it for
- * calls of up to n_residues residues (< 2^32 - 128; n_seq < 2^31 is checked, nothing is kept
- * per protein): 8 bytes per residue of HBM (the distinct-kmer sets of proteins too long for
- * LDS). kma_workspace_reserve(ws, n) = _reserve_batch(ws, n, n / 16 + 256). These are the only
- * calls that allocate.                                                                       */
+ * calls of up to n_residues residues (<= 2^32 - 128, more is KMA_E_INVALID; n_seq < 2^31 is
+ * checked, nothing is kept per protein): 8 bytes per residue of HBM (the distinct-kmer sets of
+ * proteins too long for LDS) and 0.625 bytes per residue for the stream of calls that pack
+ * (kma_packed_bytes): 34.4 + 2.7 GB at the limit. kma_workspace_reserve(ws, n) =
+ * _reserve_batch(ws, n, n / 16 + 256). These are the only calls that allocate.               */
 int kma_workspace_create(int device, kma_workspace** out);
 int kma_workspace_reserve(kma_workspace* ws, uint64_t n_residues);
 int kma_workspace_reserve_batch(kma_workspace* ws, uint64_t n_residues, uint64_t n_seq);
@@ -359,7 +360,8 @@ int kma_annotate_proteins(const kma_table* table, const uint8_t* residues,
                           uint32_t* out_tally, uint32_t n_fid);
 /* Device form: every pointer is device memory on the workspace's device (the table has a
  * replica there); `d_residues` is 8-byte aligned and readable for 32 bytes past
- * offsets[n_seq]; n_residues = offsets[n_seq] - offsets[0] (<= the workspace reservation);
+ * offsets[n_seq]; n_residues = offsets[n_seq] - offsets[0] (<= the workspace reservation, which
+ * is 8 bytes per residue, and <= 2^32 - 128: more in one call is KMA_E_INVALID);
  * d_tally (n_fid u32) is accumulated into, not cleared. Asynchronous on `stream`: one kernel
  * launch (annotate_kernel: each window probes the table where it stands, per-protein sets and
  * the vote in LDS), preceded by a pack kernel into the workspace under KMA_OPT_PACKED_INPUT
@@ -382,7 +384,8 @@ int kma_annotate_proteins_device(const kma_table* table, kma_workspace* ws,
  *                       codes (table NULL: the standard alphabet); no device needed
  *   kma_annotate_packed_device : kma_annotate_proteins_device on a packed stream already in
  *                       device memory (8-byte aligned): stream residue 0 is residue
- *                       d_offsets[0]; one kernel launch.                                      */
+ *                       d_offsets[0]; one kernel launch. The same limits: n_residues <= the
+ *                       workspace reservation and <= 2^32 - 128.                              */
 uint64_t kma_packed_bytes(uint64_t n_residues);
 int kma_pack_residues(const kma_table* table, const uint8_t* residues, uint64_t n, uint8_t* out,
                       uint64_t out_bytes);

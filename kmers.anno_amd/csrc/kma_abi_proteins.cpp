@@ -636,6 +636,9 @@ int kma_annotate_proteins_device(const kma_table* t, kma_workspace* ws, const ui
   if (!d_residues || !d_offsets || !d_fid || !d_count || !d_status)
     return fail(KMA_E_INVALID, "null device buffer");
   if ((uintptr_t)d_residues & 7) return fail(KMA_E_INVALID, "residues must be 8-byte aligned");
+  if (n_residues > kMaxResidues)
+    return fail(KMA_E_INVALID, "%llu residues in one call (limit 2^32 - 128)",
+                (unsigned long long)n_residues);
   if (n_residues > ws->res_cap)
     return fail(KMA_E_CAPACITY, "workspace reserved for %llu residues, call needs %llu",
                 (unsigned long long)ws->res_cap, (unsigned long long)n_residues);
@@ -691,6 +694,9 @@ int kma_annotate_packed_device(const kma_table* t, kma_workspace* ws, const uint
   if (!d_stream || !d_offsets || !d_fid || !d_count || !d_status)
     return fail(KMA_E_INVALID, "null device buffer");
   if ((uintptr_t)d_stream & 7) return fail(KMA_E_INVALID, "stream must be 8-byte aligned");
+  if (n_residues > kMaxResidues)
+    return fail(KMA_E_INVALID, "%llu residues in one call (limit 2^32 - 128)",
+                (unsigned long long)n_residues);
   if (n_residues > ws->res_cap)
     return fail(KMA_E_CAPACITY, "workspace reserved for %llu residues, call needs %llu",
                 (unsigned long long)ws->res_cap, (unsigned long long)n_residues);
