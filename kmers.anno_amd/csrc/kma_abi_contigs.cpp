@@ -95,7 +95,7 @@ int contig_shard(kma_table* t, const Replica& r, const uint8_t* dna, const uint6
   KMA_HIP(c->h_in.reserve(in_bytes + off_bytes + tb));
   uint8_t* hin = c->h_in.p;
   hipStream_t s = c->stream;
-  KMA_HIP(stage_h2d(c->d_in.p, hin, dna + base, total, r.device, s));
+  KMA_HIP(stage_h2d(c->d_in.p, hin, dna + base, total, s));
   std::memset(hin + total, 0, in_bytes - total);
   KMA_HIP(hipMemcpyAsync(c->d_in.p + total, hin + total, in_bytes - total,
                          hipMemcpyHostToDevice, s));

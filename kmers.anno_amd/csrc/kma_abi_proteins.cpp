@@ -151,58 +151,47 @@ int check_protein_call(const kma_table* t, int min_hits, uint32_t flags) {
   if (flags & ~(KMA_F_END_EXCLUSIVE | KMA_F_MULTISET)) return fail(KMA_E_INVALID, "bad flags");
   return KMA_OK;
 }
+
+// The argument checks of the device entry points; d_in is the residues or the packed stream
+// (`what` in the alignment message). *out: the table's replica on the workspace's device. A call
+// of no proteins passes without its buffers being looked at (the caller returns then).
+int check_device_call(const kma_table* t, const kma_workspace* ws, const uint8_t* d_in,
+                      const char* what, const uint64_t* d_offsets, uint32_t n_seq,
+                      uint64_t n_residues, int min_hits, uint32_t flags, const int32_t* d_fid,
+                      const int32_t* d_count, const uint8_t* d_status, Replica* out) {
+  if (int rc = check_protein_call(t, min_hits, flags)) return rc;
+  if (!ws) return fail(KMA_E_INVALID, "null workspace");
+  if (!replica_on(t, ws->device, out))
+    return fail(KMA_E_INVALID, "table has no replica on the workspace's device %d", ws->device);
+  if (n_seq == 0) return KMA_OK;
+  if (!d_in || !d_offsets || !d_fid || !d_count || !d_status)
+    return fail(KMA_E_INVALID, "null device buffer");
+  if ((uintptr_t)d_in & 7) return fail(KMA_E_INVALID, "%s must be 8-byte aligned", what);
+  if (n_residues > kMaxResidues)
+    return fail(KMA_E_INVALID, "%llu residues in one call (limit 2^32 - 128)",
+                (unsigned long long)n_residues);
+  if (n_residues > ws->res_cap)
+    return fail(KMA_E_CAPACITY, "workspace reserved for %llu residues, call needs %llu",
+                (unsigned long long)ws->res_cap, (unsigned long long)n_residues);
+  return KMA_OK;
+}
 }  // namespace
 
-// One shard [lo, hi) of a host protein call on replica r (host buffers, synchronous).
-// Host bytes -> pinned staging -> device, pipelined: the input is cut into pieces of whole
-// proteins, one kernel per piece. ASCII input (stage_h2d): the staging pool copies piece i's
-// part of the pinned buffer in 2 MiB chunks and ONE copy per piece goes on the copy stream, so
-// piece i + 1 is staged while piece i's copy and kernel run (r04g's trace of 153 chunk-sized
-// copies kept the DMA engine idle a quarter of the time, profiles/r04/e2e_trace_r04g.json).
-// Packed input (the default): streamed segments, below in protein_shard.
+// Host bytes -> pinned staging -> device: the staging pool copies the bytes into the pinned
+// buffer in 2 MiB chunks and ONE copy goes on s (r04g's trace of 153 chunk-sized copies kept the
+// DMA engine idle a quarter of the time, profiles/r04/e2e_trace_r04g.json).
 hipError_t kma::host::stage_h2d(uint8_t* d_dst, uint8_t* h_pinned, const uint8_t* src, size_t len,
-                                int device, hipStream_t s) {
+                                hipStream_t s) {
   constexpr size_t kChunk = 2u << 20;
   const size_t n_chunks = (len + kChunk - 1) / kChunk;
   staging_pool().run(n_chunks, staging_threads(), [&](uint64_t i) {
     const size_t off = i * kChunk;
     std::memcpy(h_pinned + off, src + off, std::min(kChunk, len - off));
   });
-  (void)device;
   return len ? hipMemcpyAsync(d_dst, h_pinned, len, hipMemcpyHostToDevice, s) : hipSuccess;
 }
 
 namespace {
-// The packed form of stage_h2d (piece-wise copies, kStreamedCopies = 0): stream groups [ga, gb)
-// (64 residues, 40 bytes each) packed from src (residue 64 ga onwards; residues past n_res read
-// as no code) into the pinned buffer in chunks of 2^15 groups (2M residues) on the staging
-// pool, then copied to d_stream in one copy; `tail` extra zero bytes (the kernel's read
-// padding) follow the last group.
-hipError_t stage_pack_h2d(uint8_t* d_stream, uint8_t* h_stream, const uint8_t* lut,
-                          const uint8_t* residues, uint64_t n_res, uint64_t ga, uint64_t gb,
-                          uint64_t tail, hipStream_t s) {
-  constexpr uint64_t kChunkGroups = 1u << 15;
-  const uint64_t n_chunks = std::max<uint64_t>(1, (gb - ga + kChunkGroups - 1) / kChunkGroups);
-  staging_pool().run(n_chunks, staging_threads(), [&](uint64_t i) {
-    const uint64_t g0 = ga + i * kChunkGroups, g1 = std::min(gb, g0 + kChunkGroups);
-    const uint64_t r0 = 64 * g0, r1 = std::min(64 * g1, n_res);
-    const uint64_t bytes = 40 * (g1 - g0) + (g1 == gb ? tail : 0);
-    kma::pack_residues_host(lut, residues + r0, r1 > r0 ? r1 - r0 : 0, h_stream + 40 * g0, bytes);
-  });
-  const uint64_t bytes = 40 * (gb - ga) + tail;
-  return bytes ? hipMemcpyAsync(d_stream + 40 * ga, h_stream + 40 * ga, bytes,
-                                hipMemcpyHostToDevice, s)
-               : hipSuccess;
-}
-
-// Streamed copies of packed input (protein_shard): the stream is copied in segments as soon as
-// they are packed, instead of one copy per piece after the whole piece is packed (KMA_HOST_STREAM
-// = 0 builds the piece-wise pipeline for A/B runs).
-#ifndef KMA_HOST_STREAM
-#define KMA_HOST_STREAM 1
-#endif
-constexpr bool kStreamedCopies = KMA_HOST_STREAM != 0;
-
 // Host-side phase times of the last host protein shard call (kma_debug_host_profile, for the
 // host-call measurements in scripts/e2e_host.py): ms in setup (context, reservations, offsets),
 // staging (packing / copying into pinned memory and queueing the copies), launches, the final
@@ -217,6 +206,196 @@ double ms_since(Clock::time_point a) {
   return std::chrono::duration<double, std::milli>(Clock::now() - a).count();
 }
 
+// One shard of a host protein call on one replica, while the call runs. Host bytes -> pinned
+// staging -> device, pipelined: the shard is cut into pieces of whole proteins (plan), one kernel
+// per piece on the compute stream s, behind the piece's input on the copy streams; a piece's
+// outputs go back on the d2h stream while later pieces copy and run. The call's inputs are fixed
+// at construction; bind() takes the pointers into the context's buffers once protein_shard has
+// reserved them, then protein_shard sets the plan.
+struct Shard {
+  kma_table* const t;
+  const Replica& r;
+  HostCtx* const c;
+  const hipStream_t s;  // c->stream
+  const ShardLayout lay;
+  const uint8_t* const residues;  // the shard's first residue in the caller's array
+  const uint64_t nres, n_groups;  // n_groups: stream groups of 64 residues
+  const bool packed;
+  const size_t in_bytes;  // the staged input with the kernel's read padding
+  const int min_hits;
+  const uint32_t flags;
+  uint8_t* hin = nullptr;          // pinned: the staged input, then the offsets
+  const uint64_t* hoff = nullptr;  // the shard's offsets rebased to 0
+  int32_t* d_fid = nullptr;
+  int32_t* d_cnt = nullptr;
+  uint32_t* d_tally = nullptr;
+  uint8_t* d_st = nullptr;
+  PiecePlan plan;
+  double t_stage = 0, t_launch = 0, t_wait = 0;  // ms (the profile)
+
+  Shard(kma_table* t, const Replica& r, HostCtx* c, ShardLayout lay, const uint8_t* residues,
+        uint64_t nres, bool packed, int min_hits, uint32_t flags)
+      : t(t), r(r), c(c), s(c->stream), lay(lay), residues(residues), nres(nres),
+        n_groups((nres + 63) / 64), packed(packed),
+        in_bytes(packed ? (size_t)kma::packed_bytes(nres) : (nres + kResPad + 7) & ~7ull),
+        min_hits(min_hits), flags(flags) {}
+  uint64_t* bind();
+  int outputs_back(int i, uint32_t a, uint32_t b);
+  int launch_piece(int i, hipStream_t cs, bool both_copies = false);
+  int stage_streamed();
+  int stage_piecewise();
+  int collect_outputs(int32_t* out_fid, int32_t* out_count, uint8_t* out_status, uint32_t* tally);
+};
+
+// The pointers into the context's reserved buffers; returns the pinned offsets array (n + 1
+// entries behind the staged input) for the caller to fill.
+uint64_t* Shard::bind() {
+  hin = c->h_in.p;
+  uint64_t* off = reinterpret_cast<uint64_t*>(hin + in_bytes);
+  hoff = off;
+  uint8_t* dout = c->d_out.p;
+  d_fid = reinterpret_cast<int32_t*>(dout + lay.fid_at);
+  d_cnt = reinterpret_cast<int32_t*>(dout + lay.count_at);
+  d_tally = lay.tally ? reinterpret_cast<uint32_t*>(dout + lay.tally_at) : nullptr;
+  d_st = dout + lay.status_at;
+  return off;
+}
+
+// Piece i's outputs back on the d2h stream once its kernel is done (fid, count, status slices;
+// the tally with the last piece), while later pieces copy and run.
+int Shard::outputs_back(int i, uint32_t a, uint32_t b) {
+  KMA_HIP(hipEventRecord(c->piece_done[i], s));
+  KMA_HIP(hipStreamWaitEvent(c->d2h, c->piece_done[i], 0));
+  uint8_t* h = c->h_out.p;
+  if (b > a) {
+    KMA_HIP(hipMemcpyAsync(h + lay.fid_at + a * 4ull, d_fid + a, (b - a) * 4ull,
+                           hipMemcpyDeviceToHost, c->d2h));
+    KMA_HIP(hipMemcpyAsync(h + lay.count_at + a * 4ull, d_cnt + a, (b - a) * 4ull,
+                           hipMemcpyDeviceToHost, c->d2h));
+    KMA_HIP(hipMemcpyAsync(h + lay.status_at + a, d_st + a, b - a, hipMemcpyDeviceToHost, c->d2h));
+  }
+  if (i + 1 == plan.n_pieces && lay.tally)
+    KMA_HIP(hipMemcpyAsync(h + lay.tally_at, d_tally, lay.n_fid * 4ull, hipMemcpyDeviceToHost,
+                           c->d2h));
+  KMA_HIP(hipEventRecord(c->out_ready[i], c->d2h));
+  return KMA_OK;
+}
+
+// Piece i's kernel (after its input is on the device: piece_ready[i] on copy stream cs, and
+// with both_copies, piece_ready2[i] on copy[1] as well) and the copy of its outputs.
+int Shard::launch_piece(int i, hipStream_t cs, bool both_copies) {
+  const uint32_t a = plan.pbeg[i], b = plan.pbeg[i + 1];
+  KMA_HIP(hipEventRecord(c->piece_ready[i], cs));
+  KMA_HIP(hipStreamWaitEvent(s, c->piece_ready[i], 0));
+  if (both_copies) {
+    KMA_HIP(hipEventRecord(c->piece_ready2[i], c->copy[1]));
+    KMA_HIP(hipStreamWaitEvent(s, c->piece_ready2[i], 0));
+  }
+  if (b > a)
+    if (int rc = annotate_proteins_on(t, r, c->ws, c->d_in.p, c->d_off.p + a, b - a,
+                                      hoff[b] - hoff[a], min_hits, flags, d_fid + a, d_cnt + a,
+                                      d_st + a, d_tally, lay.n_fid, s,
+                                      packed ? Input::kStream : Input::kAscii, hoff[a]))
+      return rc;
+  return outputs_back(i, a, b);
+}
+
+// Packed input: the whole stream is packed by ONE staging-pool job in chunks, in stream order,
+// and the calling thread copies it in segments (plan_segments: never across a piece boundary) as
+// soon as a segment's chunks are all packed, packing chunks itself while it waits; a piece's
+// kernel follows its last segment. (Packing a whole piece before its one copy left the link
+// idle while each piece was packed: DESIGN 5, "The host call".)
+int Shard::stage_streamed() {
+  const SegShape shape;
+  const SegPlan sp = plan_segments(plan, hoff, n_groups, shape);
+  const std::vector<Seg>& segs = sp.segs;
+  const uint64_t tail = in_bytes - 40 * n_groups;  // the kernel's read padding, zeroed
+  std::unique_ptr<std::atomic<uint32_t>[]> left(new std::atomic<uint32_t>[segs.size()]);
+  for (size_t k = 0; k < segs.size(); ++k) left[k].store(segs[k].chunks, std::memory_order_relaxed);
+  int rc_copy = KMA_OK;
+  staging_pool().run_with(
+      sp.chunk_seg.size(), staging_threads(),
+      [&](uint64_t ci) {
+        const Seg& sg = segs[sp.chunk_seg[ci]];
+        const uint64_t g0 = sp.chunk_g0[ci], g1 = std::min(sg.g1, g0 + shape.chunk_groups);
+        const uint64_t r0 = 64 * g0, r1 = std::min(64 * g1, nres);
+        const uint64_t bytes = 40 * (g1 - g0) + (g1 == n_groups ? tail : 0);
+        kma::pack_residues_host(t->lut, residues + r0, r1 > r0 ? r1 - r0 : 0, hin + 40 * g0,
+                                bytes);
+        left[sp.chunk_seg[ci]].fetch_sub(1, std::memory_order_release);
+      },
+      [&](auto& help) {
+        for (size_t k = 0; k < segs.size() && rc_copy == KMA_OK; ++k) {
+          const Clock::time_point t_w = Clock::now();
+          while (left[k].load(std::memory_order_acquire) != 0)
+            if (!help()) std::this_thread::yield();
+          const Clock::time_point t_issue = Clock::now();
+          t_stage += std::chrono::duration<double, std::milli>(t_issue - t_w).count();
+          const Seg& sg = segs[k];
+          // Segments alternate over the two copy streams (two DMA engines: 52 vs 44 GB/s on
+          // one stream, profiles/r05/e2e_streamed_fifo_r05i), in stream order on each, and a
+          // piece's kernel waits for both: a piece's data lands as early as the link allows.
+          hipStream_t cs = c->copy[0];
+          if (k & 1) cs = c->copy[1];
+          const uint64_t bytes = 40 * (sg.g1 - sg.g0) + (sg.g1 == n_groups ? tail : 0);
+          if (sg.g1 == n_groups && sg.chunks == 0) std::memset(hin + 40 * n_groups, 0, tail);
+          if (bytes) {
+            const hipError_t e = hipMemcpyAsync(c->d_in.p + 40 * sg.g0, hin + 40 * sg.g0, bytes,
+                                                hipMemcpyHostToDevice, cs);
+            if (e != hipSuccess)
+              rc_copy = fail(KMA_E_DEVICE, "hipMemcpyAsync: %s", hipGetErrorString(e));
+          }
+          if (rc_copy == KMA_OK && sg.last) rc_copy = launch_piece(sg.piece, c->copy[0], true);
+          t_launch += ms_since(t_issue);
+        }
+        while (help()) {}  // (after an error: the job still completes)
+      });
+  return rc_copy;
+}
+
+// ASCII input: the staging pool copies piece i's part into the pinned buffer and ONE copy per
+// piece (stage_h2d) goes on copy stream i % 2, so piece i + 1 is staged while piece i's copy and
+// kernel run; the zero padding follows the last piece.
+int Shard::stage_piecewise() {
+  for (int i = 0; i < plan.n_pieces; ++i) {
+    hipStream_t cs = c->copy[i & 1];
+    const Clock::time_point t_piece = Clock::now();
+    const uint64_t ra = hoff[plan.pbeg[i]];
+    const uint64_t rb = i + 1 < plan.n_pieces ? hoff[plan.pbeg[i + 1]] : nres;
+    KMA_HIP(stage_h2d(c->d_in.p + ra, hin + ra, residues + ra, rb - ra, cs));
+    if (i + 1 == plan.n_pieces) {
+      std::memset(hin + nres, 0, in_bytes - nres);
+      KMA_HIP(hipMemcpyAsync(c->d_in.p + nres, hin + nres, in_bytes - nres, hipMemcpyHostToDevice,
+                             cs));
+    }
+    const Clock::time_point t_staged = Clock::now();
+    t_stage += std::chrono::duration<double, std::milli>(t_staged - t_piece).count();
+    if (int rc = launch_piece(i, cs)) return rc;
+    t_launch += ms_since(t_staged);
+  }
+  return KMA_OK;
+}
+
+// Pieces' outputs into the caller's arrays (of the shard's first protein onwards) as they
+// arrive: the later pieces still copy and run meanwhile.
+int Shard::collect_outputs(int32_t* out_fid, int32_t* out_count, uint8_t* out_status,
+                           uint32_t* tally) {
+  const uint8_t* h = c->h_out.p;
+  for (int i = 0; i < plan.n_pieces; ++i) {
+    const Clock::time_point t_w = Clock::now();
+    KMA_HIP(hipEventSynchronize(c->out_ready[i]));
+    t_wait += ms_since(t_w);
+    const uint32_t a = plan.pbeg[i], b = plan.pbeg[i + 1];
+    if (b == a) continue;
+    pool_memcpy(out_fid + a, h + lay.fid_at + a * 4ull, (b - a) * 4ull);
+    pool_memcpy(out_count + a, h + lay.count_at + a * 4ull, (b - a) * 4ull);
+    pool_memcpy(out_status + a, h + lay.status_at + a, b - a);
+  }
+  if (lay.tally) std::memcpy(tally, h + lay.tally_at, lay.n_fid * 4ull);
+  return KMA_OK;
+}
+
+// One shard [lo, hi) of a host protein call on replica r (host buffers, synchronous).
 int protein_shard(kma_table* t, const Replica& r, int rep, const uint8_t* residues,
                   const uint64_t* offsets, uint32_t lo, uint32_t hi, int min_hits,
                   uint32_t flags, int32_t* out_fid, int32_t* out_count, uint8_t* out_status,
@@ -224,7 +403,6 @@ int protein_shard(kma_table* t, const Replica& r, int rep, const uint8_t* residu
   const uint32_t n = hi - lo;
   if (n == 0) return KMA_OK;
   const Clock::time_point t_call = Clock::now();
-  double t_stage = 0, t_launch = 0;
   const uint64_t base = offsets[lo], nres = offsets[hi] - base;
   if (nres > kMaxResidues)
     return fail(KMA_E_INVALID, "a protein of %llu residues (limit 2^32 - 128)",
@@ -236,240 +414,35 @@ int protein_shard(kma_table* t, const Replica& r, int rep, const uint8_t* residu
   if (ds.err != hipSuccess) return fail(KMA_E_DEVICE, "hipSetDevice(%d)", r.device);
   // KMA_OPT_PACKED_INPUT (default): residues are packed to 5 bits while they are staged (the
   // H2D moves 0.625 bytes per residue) and the packed kernel reads the stream.
-  const bool packed = opt(KMA_OPT_PACKED_INPUT) != 0;
-  const uint64_t n_groups = (nres + 63) / 64;
-  const size_t in_bytes = packed ? (size_t)kma::packed_bytes(nres) : (nres + kResPad + 7) & ~7ull;
+  Shard sh(t, r, c, ShardLayout(n, n_fid, tally != nullptr), residues + base, nres,
+           opt(KMA_OPT_PACKED_INPUT) != 0, min_hits, flags);
   const size_t off_bytes = (n + 1) * 8ull;
-  const size_t out_bytes = n * 9ull + (tally ? n_fid * 4ull : 0) + 16;
-  KMA_HIP(c->d_in.reserve(in_bytes));
+  KMA_HIP(c->d_in.reserve(sh.in_bytes));
   KMA_HIP(c->d_off.reserve(n + 1));
-  KMA_HIP(c->d_out.reserve(out_bytes));
-  KMA_HIP(c->h_in.reserve(in_bytes + off_bytes));
-  KMA_HIP(c->h_out.reserve(out_bytes));
+  KMA_HIP(c->d_out.reserve(sh.lay.out_bytes));
+  KMA_HIP(c->h_in.reserve(sh.in_bytes + off_bytes));
+  KMA_HIP(c->h_out.reserve(sh.lay.out_bytes));
   if (int rc = kma_workspace_reserve_batch(c->ws, nres, n)) return rc;
-  // Stage: rebased offsets, then the residues (and, with the last piece, their zero padding)
-  // in pieces of whole proteins, in one pinned buffer. Piece i's copies go on copy stream
-  // i % 2 (the offsets with piece 0); the kernel of piece i waits for piece i's event on the
-  // compute stream, so the staging and transfer of piece i + 1 run under the kernel of piece i,
-  // and two pieces' copies may run at once on two DMA engines (pieces of >= kPieceBytes residues,
-  // at most KMA_HOST_PIECES (default 8, <= kMaxPieces; read per call: streamed c5 calls took
-  // 5.6-5.7 / 6.0 / 6.1 ms at 8 / 12 / 16 pieces, profiles/r05/e2e_streamed_alt_r05j);
-  // a small call is one piece). c5 whole batch: 12.5 ms as one piece, 8.6 ms in 8 (round 2,
-  // profiles/r02r_host_pipeline/).
-  const int64_t pm = opt(KMA_OPT_HOST_PIECE_MIN);
-  const uint64_t kPieceBytes = pm > 0 ? (uint64_t)pm : 16ull << 20;
-  const int64_t po = opt(KMA_OPT_HOST_PIECES);
-  // packed input: the stream is copied in segments as it is packed (kStreamedCopies)
-  const bool streamed = packed && kStreamedCopies;
-  const uint64_t max_pieces =
-      po > 0 ? std::min<uint64_t>((uint64_t)po, kMaxPieces) : 8;
-  uint8_t* hin = c->h_in.p;
-  hipStream_t s = c->stream;
-  uint64_t* hoff = reinterpret_cast<uint64_t*>(hin + in_bytes);
-  rebase_offsets(hoff, offsets + lo, (uint64_t)n + 1, base);
-  KMA_HIP(hipMemcpyAsync(c->d_off.p, hoff, off_bytes, hipMemcpyHostToDevice, c->copy[0]));
-  uint8_t* dout = c->d_out.p;
-  int32_t* d_fid = reinterpret_cast<int32_t*>(dout);
-  int32_t* d_cnt = d_fid + n;
-  uint32_t* d_tally = tally ? reinterpret_cast<uint32_t*>(d_cnt + n) : nullptr;
-  uint8_t* d_st = reinterpret_cast<uint8_t*>(d_cnt + n) + (tally ? n_fid * 4ull : 0);
-  if (d_tally) KMA_HIP(hipMemsetAsync(d_tally, 0, n_fid * 4ull, s));
-  const int n_pieces = (int)std::max<uint64_t>(1, std::min<uint64_t>(max_pieces, nres / kPieceBytes));
-  // Piece sizes. Piece-wise copies: ramp up and down (weights 1, 2, 4, ..., 4, 2, 1): a small
-  // first piece starts the link early and a small last piece shortens the tail behind the last
-  // copy (round 4's equal eighths left 0.4 ms of kernel and 0.5 ms of output copies after the
-  // last H2D, profiles/r04/e2e_trace_r04h.json). Streamed copies: the link no longer waits for
-  // a piece, only the kernels do, and those keep up with the link (0.155 vs 0.18 ms per 1/22 of
-  // c5), so equal pieces: the tail is one small piece's kernel (a ramp down's halving pieces
-  // left kernels queued behind the last copy: 0.78 ms, profiles/r05/e2e_streamed_ramp_r05f).
-  // (Also measured on streamed calls: the last four pieces shrinking geometrically, weights 0.6,
-  // 0.36, 0.22, 0.13 of the others, cut the kernel after the last copy from ~0.6 to ~0.3 ms but
-  // the calls were no faster on two boxes: 5.8-6.7 vs 5.6-7.3 ms and 6.1-6.3 vs 5.6-6.7 ms,
-  // profiles/r05/e2e_taper_r05w, r05y.)
-  uint64_t wsum = 0, wcum[kMaxPieces + 1] = {0};
-  for (int i = 0; i < n_pieces; ++i) {
-    const int edge = std::min(i, n_pieces - 1 - i);
-    wsum += streamed || n_pieces < 4 ? 1u : (1u << std::min(edge, 2));
-    wcum[i + 1] = wsum;
-  }
-  uint32_t pbeg[kMaxPieces + 1] = {0};  // first protein of each piece (relative to lo)
-  const uint8_t* hout = c->h_out.p;
-  // piece i's outputs back on the d2h stream once its kernel is done (fid, count, status
-  // slices; the tally with the last piece), while later pieces copy and run
-  auto outputs_back = [&](int i, uint32_t a, uint32_t b) -> int {
-    KMA_HIP(hipEventRecord(c->piece_done[i], s));
-    KMA_HIP(hipStreamWaitEvent(c->d2h, c->piece_done[i], 0));
-    if (b > a) {
-      uint8_t* h = c->h_out.p;
-      KMA_HIP(hipMemcpyAsync(h + a * 4ull, d_fid + a, (b - a) * 4ull, hipMemcpyDeviceToHost, c->d2h));
-      KMA_HIP(hipMemcpyAsync(h + (n + a) * 4ull, d_cnt + a, (b - a) * 4ull, hipMemcpyDeviceToHost,
-                             c->d2h));
-      KMA_HIP(hipMemcpyAsync(h + n * 8ull + (tally ? n_fid * 4ull : 0) + a, d_st + a, b - a,
-                             hipMemcpyDeviceToHost, c->d2h));
-    }
-    if (i + 1 == n_pieces && tally)
-      KMA_HIP(hipMemcpyAsync(c->h_out.p + n * 8ull, d_tally, n_fid * 4ull, hipMemcpyDeviceToHost,
-                             c->d2h));
-    KMA_HIP(hipEventRecord(c->out_ready[i], c->d2h));
-    return KMA_OK;
-  };
+  // The rebased offsets go first, on copy stream 0, from the pinned buffer that also stages the
+  // residues.
+  rebase_offsets(sh.bind(), offsets + lo, (uint64_t)n + 1, base);
+  KMA_HIP(hipMemcpyAsync(c->d_off.p, sh.hoff, off_bytes, hipMemcpyHostToDevice, c->copy[0]));
+  if (sh.d_tally) KMA_HIP(hipMemsetAsync(sh.d_tally, 0, n_fid * 4ull, sh.s));
   const double t_setup = ms_since(t_call);
-  // Piece boundaries: the first protein starting at or after each piece's residue target.
-  for (int i = 1; i < n_pieces; ++i) {
-    const uint64_t target = nres * wcum[i] / wsum;
-    pbeg[i] = (uint32_t)(std::lower_bound(hoff + pbeg[i - 1], hoff + n, target) - hoff);
-  }
-  pbeg[n_pieces] = n;
-  // Piece i's kernel (after its input is on the device: piece_ready[i] on copy stream cs, and
-  // with both_copies, piece_ready2[i] on copy[1] as well) and the copy of its outputs.
-  auto launch_piece = [&](int i, hipStream_t cs, bool both_copies = false) -> int {
-    const uint32_t a = pbeg[i], b = pbeg[i + 1];
-    KMA_HIP(hipEventRecord(c->piece_ready[i], cs));
-    KMA_HIP(hipStreamWaitEvent(s, c->piece_ready[i], 0));
-    if (both_copies) {
-      KMA_HIP(hipEventRecord(c->piece_ready2[i], c->copy[1]));
-      KMA_HIP(hipStreamWaitEvent(s, c->piece_ready2[i], 0));
-    }
-    if (b > a)
-      if (int rc = annotate_proteins_on(t, r, c->ws, c->d_in.p, c->d_off.p + a, b - a,
-                                        hoff[b] - hoff[a], min_hits, flags, d_fid + a,
-                                        d_cnt + a, d_st + a, d_tally, n_fid, s,
-                                        packed ? Input::kStream : Input::kAscii, hoff[a]))
-        return rc;
-    return outputs_back(i, a, b);
-  };
-  if (streamed) {
-    // Streamed staging: the whole stream is packed by ONE staging-pool job in chunks of
-    // kChunkGroups groups, in stream order, and the calling thread copies it in segments (at most
-    // kSegGroups groups, never across a piece boundary) as soon as a segment's chunks are all
-    // packed, packing chunks itself while it waits; a piece's kernel follows its last segment.
-    // Round 4 packed a whole piece before its one copy: the link idled while each piece was
-    // packed (0.24 and 0.30 ms gaps while the pieces ramped up, profiles/r05/e2e_piecewise_r05d/events.jsonl).
-    // Segments of >= 2.6 MB keep the copies near the one-copy rate (2 MiB copies: 42 vs 51 GB/s).
-    constexpr uint64_t kChunkGroups = 1u << 12, kSegGroups = 1u << 18, kFirstSegGroups = 1u << 16;
-    const uint64_t tail = in_bytes - 40 * n_groups;  // the kernel's read padding, zeroed
-    struct Seg {
-      uint64_t g0, g1;
-      int piece;
-      bool last;  // the piece's last segment: its kernel follows the copy
-      uint32_t chunks;
-    };
-    std::vector<Seg> segs;
-    std::vector<uint32_t> chunk_seg;  // chunk -> segment
-    std::vector<uint64_t> chunk_g0;   // chunk -> first group
-    uint64_t g = 0;
-    for (int i = 0; i < n_pieces; ++i) {  // the group holding a boundary goes with the earlier piece
-      const uint64_t g1 = i + 1 < n_pieces
-                              ? std::max(g, std::min(n_groups, (hoff[pbeg[i + 1]] + 63) / 64))
-                              : n_groups;
-      do {
-        const uint64_t want = std::min(kSegGroups, kFirstSegGroups << std::min<size_t>(segs.size(), 2));
-        const uint64_t e = std::min(g1, g + want);
-        uint32_t nch = 0;
-        for (uint64_t ch = g; ch < e; ch += kChunkGroups, ++nch) {
-          chunk_seg.push_back((uint32_t)segs.size());
-          chunk_g0.push_back(ch);
-        }
-        segs.push_back({g, e, i, e == g1, nch});
-        g = e;
-      } while (g < g1);
-    }
-    std::unique_ptr<std::atomic<uint32_t>[]> left(new std::atomic<uint32_t>[segs.size()]);
-    for (size_t k = 0; k < segs.size(); ++k) left[k].store(segs[k].chunks, std::memory_order_relaxed);
-    int rc_copy = KMA_OK;
-    staging_pool().run_with(
-        chunk_seg.size(), staging_threads(),
-        [&](uint64_t ci) {
-          const Seg& sg = segs[chunk_seg[ci]];
-          const uint64_t g0 = chunk_g0[ci], g1 = std::min(sg.g1, g0 + kChunkGroups);
-          const uint64_t r0 = 64 * g0, r1 = std::min(64 * g1, nres);
-          const uint64_t bytes = 40 * (g1 - g0) + (g1 == n_groups ? tail : 0);
-          kma::pack_residues_host(t->lut, residues + base + r0, r1 > r0 ? r1 - r0 : 0,
-                                  hin + 40 * g0, bytes);
-          left[chunk_seg[ci]].fetch_sub(1, std::memory_order_release);
-        },
-        [&](auto& help) {
-          for (size_t k = 0; k < segs.size() && rc_copy == KMA_OK; ++k) {
-            const Clock::time_point t_w = Clock::now();
-            while (left[k].load(std::memory_order_acquire) != 0)
-              if (!help()) std::this_thread::yield();
-            const Clock::time_point t_issue = Clock::now();
-            t_stage += std::chrono::duration<double, std::milli>(t_issue - t_w).count();
-            const Seg& sg = segs[k];
-            // (The copies run at ~57 GB/s until the first piece kernel starts, then at ~36 GB/s:
-            // the engines' writes into HBM share the fabric with the probe's gathers at their
-            // request ceiling. Measured and not kept: the piece kernels reading the packed stream
-            // from the pinned buffer over PCIe instead, 5.5 vs 3.4 ms of kernels, calls 7.1-7.7
-            // vs 5.3-7.0 ms; the pool packing straight into fine-grained device memory through the
-            // BAR, 44 GB/s alone and 7.9 ms beside a DMA that takes 3.4 ms alone, where packing
-            // into pinned memory beside it takes 3.4 ms: profiles/r05/host_paths_r05/; and the
-            // piece kernels but the last on a CU-masked stream (half the CUs), to leave the copies
-            // fabric: no effect in one process alternating both, 5.22-5.47 vs 5.25-5.39 ms,
-            // profiles/r05/host_cu_mask/.)
-            // Segments alternate over the two copy streams (two DMA engines: 52 vs 44 GB/s on
-            // one stream, profiles/r05/e2e_streamed_fifo_r05i), in stream order on each, and a
-            // piece's kernel waits for both: a piece's data lands as early as the link allows.
-            // (Round 5's first build put whole pieces on alternate streams: consecutive pieces
-            // shared the link and every other kernel waited ~0.09 ms for its data,
-            // profiles/r05/e2e_streamed_r05h.)
-            hipStream_t cs = c->copy[0];
-            if (k & 1) cs = c->copy[1];
-            const uint64_t bytes = 40 * (sg.g1 - sg.g0) + (sg.g1 == n_groups ? tail : 0);
-            if (sg.g1 == n_groups && sg.chunks == 0) std::memset(hin + 40 * n_groups, 0, tail);
-            if (bytes) {
-              const hipError_t e = hipMemcpyAsync(c->d_in.p + 40 * sg.g0, hin + 40 * sg.g0, bytes,
-                                                  hipMemcpyHostToDevice, cs);
-              if (e != hipSuccess) rc_copy = fail(KMA_E_DEVICE, "hipMemcpyAsync: %s", hipGetErrorString(e));
-            }
-            if (rc_copy == KMA_OK && sg.last) rc_copy = launch_piece(sg.piece, c->copy[0], true);
-            t_launch += ms_since(t_issue);
-          }
-          while (help()) {}  // (after an error: the job still completes)
-        });
-    if (rc_copy) return rc_copy;
-  } else {
-    uint64_t ga = 0;  // packed: first stream group the piece stages
-    for (int i = 0; i < n_pieces; ++i) {
-      hipStream_t cs = c->copy[i & 1];
-      const Clock::time_point t_piece = Clock::now();
-      const uint64_t ra = hoff[pbeg[i]], rb = i + 1 < n_pieces ? hoff[pbeg[i + 1]] : nres;
-      if (packed) {  // the group holding the piece boundary goes with the earlier piece
-        const uint64_t gb = i + 1 < n_pieces ? std::min(n_groups, (rb + 63) / 64) : n_groups;
-        KMA_HIP(stage_pack_h2d(c->d_in.p, hin, t->lut, residues + base, nres, ga, gb,
-                               i + 1 == n_pieces ? in_bytes - 40 * n_groups : 0, cs));
-        ga = gb;
-      } else {
-        KMA_HIP(stage_h2d(c->d_in.p + ra, hin + ra, residues + base + ra, rb - ra, r.device, cs));
-        if (i + 1 == n_pieces) {
-          std::memset(hin + nres, 0, in_bytes - nres);
-          KMA_HIP(hipMemcpyAsync(c->d_in.p + nres, hin + nres, in_bytes - nres,
-                                 hipMemcpyHostToDevice, cs));
-        }
-      }
-      const Clock::time_point t_staged = Clock::now();
-      t_stage += std::chrono::duration<double, std::milli>(t_staged - t_piece).count();
-      if (int rc = launch_piece(i, cs)) return rc;
-      t_launch += ms_since(t_staged);
-    }
-  }
-  // Pieces' outputs into the caller's arrays as they arrive (the later pieces still copy and
-  // run meanwhile).
-  double t_wait = 0;
+  // Pieces of >= KMA_OPT_HOST_PIECE_MIN residues (default 16 Mi), at most KMA_OPT_HOST_PIECES
+  // (default 8; read per call), so a small call is one piece. Streamed calls cut equal pieces:
+  // the link does not wait for a piece there, only the kernels do, and a ramp down left kernels
+  // queued behind the last copy. Piece-wise (ASCII) calls ramp (plan_pieces).
+  const int64_t pm = opt(KMA_OPT_HOST_PIECE_MIN), po = opt(KMA_OPT_HOST_PIECES);
+  sh.plan = plan_pieces(sh.hoff, n, nres, pm > 0 ? (uint64_t)pm : 16ull << 20,
+                        po > 0 ? (uint64_t)po : 8, /*ramp=*/!sh.packed);
+  if (int rc = sh.packed ? sh.stage_streamed() : sh.stage_piecewise()) return rc;
   const Clock::time_point t_o = Clock::now();
-  for (int i = 0; i < n_pieces; ++i) {
-    const Clock::time_point t_w = Clock::now();
-    KMA_HIP(hipEventSynchronize(c->out_ready[i]));
-    t_wait += ms_since(t_w);
-    const uint32_t a = pbeg[i], b = pbeg[i + 1];
-    if (b == a) continue;
-    pool_memcpy(out_fid + lo + a, hout + a * 4ull, (b - a) * 4ull);
-    pool_memcpy(out_count + lo + a, hout + (n + a) * 4ull, (b - a) * 4ull);
-    pool_memcpy(out_status + lo + a, hout + n * 8ull + (tally ? n_fid * 4ull : 0) + a, b - a);
-  }
-  if (tally) std::memcpy(tally, hout + n * 8ull, n_fid * 4ull);
+  if (int rc = sh.collect_outputs(out_fid + lo, out_count + lo, out_status + lo, tally)) return rc;
   {
-    const double p[kProfFields] = {t_setup, t_stage, t_launch, t_wait, ms_since(t_o) - t_wait,
-                                   ms_since(t_call), (double)staging_threads(), (double)n_pieces};
+    const double p[kProfFields] = {
+        t_setup,          sh.t_stage, sh.t_launch, sh.t_wait, ms_since(t_o) - sh.t_wait,
+        ms_since(t_call), (double)staging_threads(), (double)sh.plan.n_pieces};
     std::lock_guard<std::mutex> g(g_prof_mu);
     std::copy(p, p + kProfFields, g_prof);
     if (rep < kProfReplicas) std::copy(p, p + kProfFields, g_prof_rep[rep]);
@@ -626,28 +599,17 @@ int kma_annotate_proteins_device(const kma_table* t, kma_workspace* ws, const ui
                                  int min_hits, uint32_t flags, int32_t* d_fid, int32_t* d_count,
                                  uint8_t* d_status, uint32_t* d_tally, uint32_t n_fid,
                                  void* stream) {
-  if (int rc = check_protein_call(t, min_hits, flags)) return rc;
-  if (!ws) return fail(KMA_E_INVALID, "null workspace");
   Replica rep;
-  if (!replica_on(t, ws->device, &rep))
-    return fail(KMA_E_INVALID, "table has no replica on the workspace's device %d", ws->device);
-  const Replica* r = &rep;
+  if (int rc = check_device_call(t, ws, d_residues, "residues", d_offsets, n_seq, n_residues,
+                                 min_hits, flags, d_fid, d_count, d_status, &rep))
+    return rc;
   if (n_seq == 0) return KMA_OK;
-  if (!d_residues || !d_offsets || !d_fid || !d_count || !d_status)
-    return fail(KMA_E_INVALID, "null device buffer");
-  if ((uintptr_t)d_residues & 7) return fail(KMA_E_INVALID, "residues must be 8-byte aligned");
-  if (n_residues > kMaxResidues)
-    return fail(KMA_E_INVALID, "%llu residues in one call (limit 2^32 - 128)",
-                (unsigned long long)n_residues);
-  if (n_residues > ws->res_cap)
-    return fail(KMA_E_CAPACITY, "workspace reserved for %llu residues, call needs %llu",
-                (unsigned long long)ws->res_cap, (unsigned long long)n_residues);
   const bool pack = pack_on_device(n_residues);
   if (pack)
     if (int rc = ensure_packed(ws)) return rc;
-  DeviceScope ds(r->device);
-  if (ds.err != hipSuccess) return fail(KMA_E_DEVICE, "hipSetDevice(%d)", r->device);
-  return annotate_proteins_on(t, *r, ws, d_residues, d_offsets, n_seq, n_residues, min_hits,
+  DeviceScope ds(rep.device);
+  if (ds.err != hipSuccess) return fail(KMA_E_DEVICE, "hipSetDevice(%d)", rep.device);
+  return annotate_proteins_on(t, rep, ws, d_residues, d_offsets, n_seq, n_residues, min_hits,
                               flags, d_fid, d_count, d_status, d_tally, n_fid,
                               static_cast<hipStream_t>(stream),
                               pack ? Input::kPackOnDevice : Input::kAscii);
@@ -685,21 +647,11 @@ int kma_annotate_packed_device(const kma_table* t, kma_workspace* ws, const uint
                                int min_hits, uint32_t flags, int32_t* d_fid, int32_t* d_count,
                                uint8_t* d_status, uint32_t* d_tally, uint32_t n_fid,
                                void* stream) {
-  if (int rc = check_protein_call(t, min_hits, flags)) return rc;
-  if (!ws) return fail(KMA_E_INVALID, "null workspace");
   Replica rep;
-  if (!replica_on(t, ws->device, &rep))
-    return fail(KMA_E_INVALID, "table has no replica on the workspace's device %d", ws->device);
+  if (int rc = check_device_call(t, ws, d_stream, "stream", d_offsets, n_seq, n_residues,
+                                 min_hits, flags, d_fid, d_count, d_status, &rep))
+    return rc;
   if (n_seq == 0) return KMA_OK;
-  if (!d_stream || !d_offsets || !d_fid || !d_count || !d_status)
-    return fail(KMA_E_INVALID, "null device buffer");
-  if ((uintptr_t)d_stream & 7) return fail(KMA_E_INVALID, "stream must be 8-byte aligned");
-  if (n_residues > kMaxResidues)
-    return fail(KMA_E_INVALID, "%llu residues in one call (limit 2^32 - 128)",
-                (unsigned long long)n_residues);
-  if (n_residues > ws->res_cap)
-    return fail(KMA_E_CAPACITY, "workspace reserved for %llu residues, call needs %llu",
-                (unsigned long long)ws->res_cap, (unsigned long long)n_residues);
   DeviceScope ds(rep.device);
   if (ds.err != hipSuccess) return fail(KMA_E_DEVICE, "hipSetDevice(%d)", rep.device);
   return annotate_proteins_on(t, rep, ws, d_stream, d_offsets, n_seq, n_residues, min_hits, flags,

@@ -240,7 +240,7 @@ uint32_t offsets_decrease_at(const uint64_t* offsets, uint32_t n);
 void pool_memcpy(void* dst, const void* src, size_t n);
 // Host bytes -> pinned staging (on the pool) -> one copy on s (kma_abi_proteins.cpp).
 hipError_t stage_h2d(uint8_t* d_dst, uint8_t* h_pinned, const uint8_t* src, size_t len,
-                     int device, hipStream_t s);
+                     hipStream_t s);
 
 // Run f(i) for i in [0, n) on n threads (inline for one) and return the first failure, with
 // its message moved to the calling thread (kma_last_error is thread-local).

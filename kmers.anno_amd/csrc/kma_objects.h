@@ -3,6 +3,7 @@
 // the kma_abi_*.cpp units; private to the library, not installed.
 #pragma once
 #include "kma_host.h"
+#include "kma_shard_plan.h"
 
 // ---- objects ---------------------------------------------------------------------------------
 struct kma_workspace {
@@ -47,8 +48,8 @@ struct Replica {
   uint8_t* d_lut = nullptr;
 };
 
-// Per-call resources of the host entry points on one device (kept in the table's pool).
-constexpr int kMaxPieces = 16;  // host protein calls: H2D / kernel pipeline depth (events)
+// Per-call resources of the host entry points on one device (kept in the table's pool); a
+// protein call uses one set of events per piece (kMaxPieces, kma_shard_plan.h).
 struct HostCtx {
   int device = 0;
   hipStream_t stream = nullptr;
