@@ -609,6 +609,44 @@ int kma_protein_best_match(const uint8_t* residues, const uint64_t* offsets, uin
                            const uint32_t* cand, uint32_t n_query, double max_dist, int device,
                            int32_t* out_best, double* out_best_dist);
 
+/* ---- sequence MD5 and the duplicate check (added under ABI 7) ----------------------------------
+ * The key the reference's commands give a protein is the MD5 of its sequence
+ * (MD5Hex.sequenceMD5, Feature.getMD5: seqCheck, hashAnno, updateJson's aa_sequence_md5). A
+ * digest is the 16 bytes of RFC 1321 in its byte order (hex of byte 0 first is the usual
+ * string). flags: 0 hashes the bytes as they stand; KMA_MD5_UPPER folds 'a'..'z' to 'A'..'Z'
+ * first and touches no other byte (taken to be MD5Hex's normalisation, which is external:
+ * DESIGN.md §7). Sequence s is residues[offsets[s] .. offsets[s + 1]), starting at any byte.
+ *
+ * kma_sequence_md5_device: every pointer is device memory on `device`; d_residues is 8-byte
+ * aligned and readable for 32 bytes past offsets[n_seq] (the layout and padding of
+ * kma_annotate_proteins_device; offsets[0] need not be 0, and nothing before the aligned word
+ * of residue offsets[0] is read); n_residues = offsets[n_seq] - offsets[0] <= 2^32 - 128;
+ * d_digest (16-byte aligned) gets 16 bytes per sequence. Asynchronous on `stream`: one kernel
+ * launch, no allocation, no state left behind (it may be captured in a graph). n_seq == 0 is a
+ * no-op.
+ * kma_sequence_md5: host buffers, synchronous; the library pads its own device copy.
+ * kma_check_sequences: SequenceCheckProcessor.java:92-133 in one call: the digests, a stable
+ * sort of (digest, index), and per run of equal digests its size and the minimum and maximum of
+ * fun (optional: the caller's function id of every sequence). out_rep[s] = the smallest index
+ * whose digest equals that of s, out_size[s] = the members of its group, out_mixed[s] = 1 iff
+ * the group has more than one member and more than one fun (0 without fun). An empty sequence
+ * joins no group (:96): rep -1, size 0, mixed 0. out_stats[3] = {groups, groups of more than one
+ * member, mixed groups} (proteinMap.size(), protCount, badCount). out_digest (optional) gets
+ * the digests. Fewer than 2^31 sequences. Digest equality stands for sequence equality, as in
+ * the reference.
+ * KMA_E_INVALID before any device is touched: null arguments, decreasing offsets (host
+ * entries), unknown flag bits, more than 2^32 - 128 residues, misaligned device pointers.      */
+#define KMA_MD5_UPPER 0x1u
+int kma_sequence_md5_device(int device, const uint8_t* d_residues, const uint64_t* d_offsets,
+                            uint32_t n_seq, uint64_t n_residues, uint32_t flags,
+                            uint8_t* d_digest, void* stream);
+int kma_sequence_md5(const uint8_t* residues, const uint64_t* offsets, uint32_t n_seq,
+                     uint32_t flags, int device, uint8_t* out_digest);
+int kma_check_sequences(const uint8_t* residues, const uint64_t* offsets, uint32_t n_seq,
+                        uint32_t flags, const uint32_t* fun, int device, uint8_t* out_digest,
+                        int32_t* out_rep, uint32_t* out_size, uint8_t* out_mixed,
+                        uint64_t* out_stats);
+
 /* Window count of the 6-frame extractor before the '*'/'X' filter (for throughput metrics).  */
 uint64_t kma_contig_window_count(const uint64_t* offsets, uint32_t n_contig, int k);
 

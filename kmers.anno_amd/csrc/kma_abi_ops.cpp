@@ -1,14 +1,15 @@
 // kma_abi_ops.cpp — the projector's one-shot set operators of the C ABI (include/kmeranno.h):
-// peg table, signatures, distances / best match, peg proposals, ORF index, translation and
-// hash-annotate. Each checks its arguments on the host, enters its device, stages its batch in
+// peg table, signatures, distances / best match, peg proposals, ORF index, translation,
+// hash-annotate and the sequence MD5 / duplicate check. Each checks its arguments on the host, enters its device, stages its batch in
 // buffers of its own (kma_host.h: upload_batch, Scratch, AlphabetFlag), runs its launchers
-// (kma_proposals.hip, kma_distance.hip, kma_hashanno.hip, kma_orf.hip, kma_translate.hip) on
-// the null stream and copies the results back.
+// (kma_proposals.hip, kma_distance.hip, kma_hashanno.hip, kma_orf.hip, kma_translate.hip,
+// kma_md5.hip) on the null stream and copies the results back.
 #include <memory>
 
 #include "kma_distance.h"
 #include "kma_hashanno.h"
 #include "kma_internal.h"
+#include "kma_md5.h"
 #include "kma_objects.h"
 #include "kma_orf.h"
 #include "kma_translate.h"
@@ -757,6 +758,166 @@ int kma_hash_annotate(const uint8_t* gres, const uint64_t* goff, uint32_t n_gp,
     std::memcpy(&out_sim[i], &bits[i], 8);
     out_best[i] = (int32_t)proto[i];
   }
+  return KMA_OK;
+}
+
+}  // extern "C"
+
+// ---- sequence MD5 and the duplicate check (kma_md5.hip) ----------------------------------------
+namespace {
+constexpr uint64_t kMd5MaxResidues = (1ull << 32) - 128;
+
+// Compute units of `device` (current), asked once per device: the refill form's grid.
+int md5_compute_units(int device, uint32_t* n_cu) {
+  static std::atomic<uint32_t> known[64];
+  if (device >= 0 && device < 64)
+    if (const uint32_t c = known[device].load(std::memory_order_relaxed)) return *n_cu = c, KMA_OK;
+  int v = 0;
+  KMA_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device));
+  *n_cu = (uint32_t)std::max(v, 1);
+  if (device >= 0 && device < 64) known[device].store(*n_cu, std::memory_order_relaxed);
+  return KMA_OK;
+}
+
+// The device entry's checks (no device touched) and its one launch.
+int md5_check_device_args(const uint8_t* d_residues, const uint64_t* d_offsets, uint32_t n_seq,
+                          uint64_t n_residues, uint32_t flags, const uint8_t* d_digest) {
+  if (flags & ~(uint32_t)KMA_MD5_UPPER)
+    return fail(KMA_E_INVALID, "unknown flag bits 0x%x", flags & ~(uint32_t)KMA_MD5_UPPER);
+  if (n_seq == 0) return KMA_OK;
+  if (!d_residues || !d_offsets || !d_digest) return fail(KMA_E_INVALID, "null argument");
+  if (n_residues > kMd5MaxResidues)
+    return fail(KMA_E_INVALID, "more than 2^32 - 128 residues in one call");
+  if (reinterpret_cast<uintptr_t>(d_residues) & 7u)
+    return fail(KMA_E_INVALID, "d_residues is not 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_digest) & 15u)
+    return fail(KMA_E_INVALID, "d_digest is not 16-byte aligned");
+  return KMA_OK;
+}
+
+int md5_launch(int device, const uint8_t* d_residues, const uint64_t* d_offsets, uint32_t n_seq,
+               uint32_t flags, uint8_t* d_digest, uint32_t form, uint32_t waves_per_cu,
+               hipStream_t stream) {
+  uint32_t n_cu = 0;
+  if (int rc = md5_compute_units(device, &n_cu)) return rc;
+  kma::Md5Args a{};
+  a.res = d_residues;
+  a.off = d_offsets;
+  a.n_seq = n_seq;
+  a.n_waves = kma::md5_waves(n_seq, form, n_cu, waves_per_cu);
+  a.upper = flags & KMA_MD5_UPPER;
+  a.digest = reinterpret_cast<uint4*>(d_digest);
+  KMA_HIP(kma::launch_md5(a, form, stream));
+  return KMA_OK;
+}
+
+// The host entries' checks (no device touched).
+int md5_check_host_args(const uint8_t* residues, const uint64_t* offsets, uint32_t n_seq,
+                        uint32_t flags) {
+  if (flags & ~(uint32_t)KMA_MD5_UPPER)
+    return fail(KMA_E_INVALID, "unknown flag bits 0x%x", flags & ~(uint32_t)KMA_MD5_UPPER);
+  if (n_seq && (!residues || !offsets)) return fail(KMA_E_INVALID, "null argument");
+  return check_offsets(offsets, n_seq, "", kMd5MaxResidues + 1,
+                       "more than 2^32 - 128 residues in one call");
+}
+}  // namespace
+
+extern "C" {
+
+int kma_sequence_md5_device(int device, const uint8_t* d_residues, const uint64_t* d_offsets,
+                            uint32_t n_seq, uint64_t n_residues, uint32_t flags,
+                            uint8_t* d_digest, void* stream) {
+  if (int rc = md5_check_device_args(d_residues, d_offsets, n_seq, n_residues, flags, d_digest))
+    return rc;
+  if (n_seq == 0) return KMA_OK;
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  return md5_launch(device, d_residues, d_offsets, n_seq, flags, d_digest, kma::kMd5Default, 0,
+                    static_cast<hipStream_t>(stream));
+}
+
+// Not in kmeranno.h: measurement hook (scripts/md5_rate.py). kma_sequence_md5_device with the
+// kernel form (kma_md5.h: kMd5Static | kMd5Coop) and the refill form's waves per compute unit
+// (0: the default) chosen by the caller.
+int kma_debug_sequence_md5_device(int device, const uint8_t* d_residues,
+                                  const uint64_t* d_offsets, uint32_t n_seq, uint64_t n_residues,
+                                  uint32_t flags, uint8_t* d_digest, void* stream, uint32_t form,
+                                  uint32_t waves_per_cu) {
+  if (int rc = md5_check_device_args(d_residues, d_offsets, n_seq, n_residues, flags, d_digest))
+    return rc;
+  if (form & ~(kma::kMd5Static | kma::kMd5Coop)) return fail(KMA_E_INVALID, "unknown form");
+  if (n_seq == 0) return KMA_OK;
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  return md5_launch(device, d_residues, d_offsets, n_seq, flags, d_digest, form, waves_per_cu,
+                    static_cast<hipStream_t>(stream));
+}
+
+int kma_sequence_md5(const uint8_t* residues, const uint64_t* offsets, uint32_t n_seq,
+                     uint32_t flags, int device, uint8_t* out_digest) {
+  if (int rc = md5_check_host_args(residues, offsets, n_seq, flags)) return rc;
+  if (n_seq == 0) return KMA_OK;
+  if (!out_digest) return fail(KMA_E_INVALID, "null argument");
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  DevBufs b;
+  DevBatch in;
+  if (int rc = upload_batch(b, residues, offsets, n_seq, 32, &in)) return rc;
+  uint8_t* d_digest;
+  KMA_HIP(b.alloc(&d_digest, n_seq * 16ull));
+  if (int rc = md5_launch(device, in.bytes, in.off, n_seq, flags, d_digest, kma::kMd5Default, 0,
+                          nullptr))
+    return rc;
+  KMA_HIP(hipMemcpy(out_digest, d_digest, n_seq * 16ull, hipMemcpyDeviceToHost));
+  return KMA_OK;
+}
+
+int kma_check_sequences(const uint8_t* residues, const uint64_t* offsets, uint32_t n_seq,
+                        uint32_t flags, const uint32_t* fun, int device, uint8_t* out_digest,
+                        int32_t* out_rep, uint32_t* out_size, uint8_t* out_mixed,
+                        uint64_t* out_stats) {
+  if (!out_stats) return fail(KMA_E_INVALID, "null argument");
+  out_stats[0] = out_stats[1] = out_stats[2] = 0;
+  if (int rc = md5_check_host_args(residues, offsets, n_seq, flags)) return rc;
+  if (n_seq == 0) return KMA_OK;
+  if (!out_rep || !out_size || !out_mixed) return fail(KMA_E_INVALID, "null argument");
+  if (n_seq >= (1u << 31)) return fail(KMA_E_INVALID, "2^31 sequences or more");
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  DevBufs b;
+  DevBatch in;
+  if (int rc = upload_batch(b, residues, offsets, n_seq, 32, &in)) return rc;
+  const uint64_t n = n_seq;
+  uint8_t* d_digest;
+  uint32_t* d_fun = nullptr;
+  kma::SeqCheckArgs a{};
+  KMA_HIP(b.alloc(&d_digest, n * 16));
+  if (fun) {
+    KMA_HIP(b.alloc(&d_fun, n * 4));
+    KMA_HIP(hipMemcpy(d_fun, fun, n * 4, hipMemcpyHostToDevice));
+  }
+  for (uint64_t** p : {&a.key_a, &a.key_b}) KMA_HIP(b.alloc(p, n * 8));
+  for (uint32_t** p : {&a.idx_a, &a.idx_b, &a.start, &a.count, &a.fmin, &a.fmax, &a.size})
+    KMA_HIP(b.alloc(p, n * 4));
+  KMA_HIP(b.alloc(&a.rep, n * 4));
+  KMA_HIP(b.alloc(&a.mixed, n));
+  KMA_HIP(b.alloc(&a.stats, 24));
+  a.digest = reinterpret_cast<const uint4*>(d_digest);
+  a.off = in.off;
+  a.fun = d_fun;
+  a.n = n_seq;
+  Scratch tmp;
+  KMA_HIP(kma::launch_seq_check(a, nullptr, tmp.ask(), nullptr));
+  KMA_HIP(tmp.alloc(b));
+  if (int rc = md5_launch(device, in.bytes, in.off, n_seq, flags, d_digest, kma::kMd5Default, 0,
+                          nullptr))
+    return rc;
+  KMA_HIP(kma::launch_seq_check(a, tmp.p, tmp.bytes(), nullptr));
+  KMA_HIP(hipMemcpy(out_stats, a.stats, 24, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_rep, a.rep, n * 4, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_size, a.size, n * 4, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_mixed, a.mixed, n, hipMemcpyDeviceToHost));
+  if (out_digest) KMA_HIP(hipMemcpy(out_digest, d_digest, n * 16, hipMemcpyDeviceToHost));
   return KMA_OK;
 }
 

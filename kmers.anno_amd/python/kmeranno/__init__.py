@@ -25,6 +25,8 @@ F_END_EXCLUSIVE, F_MULTISET = 0x1, 0x2
 MAX_K = 12  # K <= 8: narrow tables (8-byte slots); 9..12: wide tables (16-byte slots)
 ORF_KEPT, ORF_REJECTED, ORF_WEAK, ORF_SMALL = 0, 1, 2, 3  # extend_proposals' status
 TR_PEG = 1  # translate_locations' flag: pegTranslate (last codon dropped, start codon -> 'M')
+MD5_UPPER = 1  # sequence_md5 / check_sequences' flag: 'a'..'z' hashed as 'A'..'Z'
+MD5_STATIC, MD5_COOP = 1, 2  # kernel forms of the measurement hook (csrc/kma_md5.h)
 
 # Every symbol include/kmeranno.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -45,6 +47,7 @@ EXPORTS = (
     "kma_table_create_from_tsv", "kma_free",
     "kma_orf_index_create", "kma_orf_index_destroy", "kma_extend_proposals",
     "kma_translate_locations",
+    "kma_sequence_md5_device", "kma_sequence_md5", "kma_check_sequences",
 )
 
 # Tuning options (include/kmeranno.h "options"): library-wide defaults read per call.
@@ -171,6 +174,12 @@ def load(path: str | None = None):
         L.kma_extend_proposals.argtypes = [_vp, _vp, _u64, C.c_double, _int, _vp, _vp, _vp, _vp]
         L.kma_translate_locations.argtypes = [_vp, _vp, _u32, _int, _int, _vp, _u64, _int, _vp,
                                               _u64, _vp]
+        L.kma_sequence_md5_device.argtypes = [_int, _vp, _vp, _u32, _u64, _u32, _vp, _vp]
+        L.kma_debug_sequence_md5_device.argtypes = [_int, _vp, _vp, _u32, _u64, _u32, _vp, _vp,
+                                                    _u32, _u32]
+        L.kma_sequence_md5.argtypes = [_vp, _vp, _u32, _u32, _int, _vp]
+        L.kma_check_sequences.argtypes = [_vp, _vp, _u32, _u32, _vp, _int, _vp, _vp, _vp, _vp,
+                                          _vp]
         L.kma_debug_translate_ms.restype = C.c_double
         L.kma_debug_translate_ms.argtypes = []
         L.kma_contig_window_count.restype = _u64
@@ -760,6 +769,63 @@ def translate_kernel_ms() -> float:
     """hipEvent time of the kernel of this thread's last translate_locations call (measurement
     hook, not in kmeranno.h)."""
     return float(load().kma_debug_translate_ms())
+
+
+def sequence_md5(residues, offsets, flags: int = 0, device: int = 0) -> np.ndarray:
+    """kma_sequence_md5: the RFC 1321 digests of a host batch (residues / offsets as
+    pack_strings gives them) on the GPU, an (n, 16) uint8 array; bytes(row).hex() is the usual
+    string. flags: MD5_UPPER folds a-z to A-Z first."""
+    residues = np.ascontiguousarray(residues, np.uint8)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    n = len(offsets) - 1
+    out = np.zeros((n, 16), np.uint8)
+    _check(load().kma_sequence_md5(residues.ctypes.data if len(residues) else None,
+                                   offsets.ctypes.data, n, flags, device,
+                                   out.ctypes.data if n else None))
+    return out
+
+
+def sequence_md5_device(d_residues: int, d_offsets: int, n_seq: int, n_residues: int,
+                        d_digest: int, flags: int = 0, device: int = 0, stream: int = 0,
+                        form: int | None = None, waves_per_cu: int = 0):
+    """kma_sequence_md5_device (asynchronous on `stream`, one kernel): device pointers, the
+    layout and padding of annotate_proteins_device; d_digest gets 16 bytes per sequence. form
+    (MD5_STATIC | MD5_COOP; measurements only) goes through the library's measurement hook."""
+    if form is None:
+        _check(load().kma_sequence_md5_device(device, d_residues or None, d_offsets or None,
+                                              n_seq, n_residues, flags, d_digest or None,
+                                              stream or None))
+    else:
+        _check(load().kma_debug_sequence_md5_device(device, d_residues or None,
+                                                    d_offsets or None, n_seq, n_residues, flags,
+                                                    d_digest or None, stream or None, form,
+                                                    waves_per_cu))
+
+
+def check_sequences(residues, offsets, fun=None, flags: int = 0, device: int = 0,
+                    digests: bool = False):
+    """kma_check_sequences (SequenceCheckProcessor.java:92-133 on the GPU): returns (rep, size,
+    mixed, stats[3] = groups, groups of more than one member, mixed groups[, digests]). rep[s]
+    = the first sequence equal to s (-1 for an empty one), size[s] its group's members, mixed[s]
+    = 1 iff that group holds more than one member and more than one of the function ids fun."""
+    residues = np.ascontiguousarray(residues, np.uint8)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    n = len(offsets) - 1
+    if fun is not None:
+        fun = np.ascontiguousarray(fun, np.uint32)
+        if len(fun) != n:
+            raise KmerAnnoError(E_INVALID, "one function id per sequence")
+    rep, size = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+    mixed, stats = np.zeros(n, np.uint8), np.zeros(3, np.uint64)
+    dig = np.zeros((n, 16), np.uint8) if digests else None
+    _check(load().kma_check_sequences(residues.ctypes.data if len(residues) else None,
+                                      offsets.ctypes.data, n, flags,
+                                      fun.ctypes.data if fun is not None and n else None, device,
+                                      dig.ctypes.data if digests and n else None,
+                                      rep.ctypes.data if n else None,
+                                      size.ctypes.data if n else None,
+                                      mixed.ctypes.data if n else None, stats.ctypes.data))
+    return (rep, size, mixed, stats, dig) if digests else (rep, size, mixed, stats)
 
 
 def hash_annotate(genome_residues, genome_offsets, proto_residues, proto_offsets, k: int = 8,
