@@ -16,6 +16,12 @@
  *   - the 6-frame contig kmer extractor
  *       proteins/kmers/KmerReference.java:157-203, KmerPosition.java:50-93
  *                                                              -> kma_annotate_contigs*
+ *   - the scoring loop of `hashAnno`, every genome against one role annotation file
+ *       proteins/kmers/anno/HashAnnotationProcessor.java:208, :233-306
+ *                                                              -> kma_hash_annotate (both sides
+ *                                                                 per call), kma_proto_index_create
+ *                                                                 once + kma_hash_annotate_indexed
+ *                                                                 per genome
  *   - ProteinKmers.distance of the gene-copy command
  *       genome/compare/GeneCopyProcessor.java:129-162          -> kma_protein_distances,
  *                                                                 kma_protein_best_match
@@ -34,7 +40,9 @@
  *   - A table is immutable after creation (replicas aside); concurrent annotate calls on one
  *     table are allowed. Host entry points take a per-device context (stream, workspace,
  *     pinned staging) from the table's pool for the call and wait on that stream only;
- *     _device calls must each use their own kma_workspace.
+ *     _device calls must each use their own kma_workspace. A prototype index
+ *     (kma_proto_index) is read-only after creation too: calls on one index may run on several
+ *     threads.
  *   - A table may hold replicas on several devices (kma_table_create_replicated /
  *     kma_table_replicate): host entry points then cut a batch into residue- (base-) balanced
  *     contiguous shards, one host thread per replica, and sum the tallies; _device calls use
@@ -181,6 +189,11 @@ int kma_device_count(int* out_n);
  *   KMA_OPT_HOST_PIECES     host protein calls: staging / kernel pipeline pieces [0: up to 8];
  *                           1..16
  *   KMA_OPT_HASH_SLICE      kma_hash_annotate: candidates per prototype slice [0: 2^31 - 1]
+ *   KMA_OPT_HASH_CAP        kma_hash_annotate_indexed: distinct candidate prototypes a genome
+ *                           protein's workgroup counts at once in its LDS table [0: 1024]; a
+ *                           protein with more is scored in prototype ranges, halved until each
+ *                           fits (results do not depend on it); 1..2048 (tests set it low).
+ *                           Its number is 12: 11 is no option, and setting it stays an error
  *   KMA_OPT_PACKED_INPUT    protein calls [1]: residues are packed to 5 bits before the probe
  *                           and the probe reads the packed stream: host calls while staging
  *                           (the H2D moves 0.625 B per residue) under 1 and 2; device calls
@@ -213,6 +226,7 @@ int kma_device_count(int* out_n);
 #define KMA_OPT_HOST_SLICE 8
 #define KMA_OPT_PLACEMENT 9
 #define KMA_OPT_HOST_PIECE_MIN 10
+#define KMA_OPT_HASH_CAP 12
 #define KMA_OPT_DEFAULT INT64_MIN
 int kma_option_set(int option, int64_t value);
 int kma_option_get(int option, int64_t* value);
@@ -570,6 +584,40 @@ int kma_hash_annotate(const uint8_t* genome_residues, const uint64_t* genome_off
                       uint32_t n_genome, const uint8_t* proto_residues,
                       const uint64_t* proto_offsets, uint32_t n_proto, int k, double min_sim,
                       int device, int32_t* out_best, double* out_sim, uint32_t* out_count);
+
+/* ---- hash annotator against a resident prototype index (added under ABI 7) -------------------
+ * hashAnno scores every genome against the same role annotation file
+ * (HashAnnotationProcessor.java:208, :259-271). kma_proto_index_create does the prototype side
+ * of kma_hash_annotate once on `device` and keeps it there: the sorted unique K-mer keys of all
+ * prototypes, per key its postings (the prototypes whose set holds it, ascending) and every
+ * prototype's set size. kma_hash_annotate_indexed then scores one genome with the semantics of
+ * kma_hash_annotate exactly (same sets, same double similarity, earlier prototypes win ties,
+ * out_count per call, KMA_E_ALPHABET on either side's call, fewer than 2^31 residues a side;
+ * n_proto == 0 or n_genome == 0: every out_best -1, out_sim 0.0, out_count 0): the genome's
+ * distinct keys are looked up in the unique keys, and one workgroup per genome protein counts
+ * the matched postings per prototype in an LDS table, scores the table and writes the protein's
+ * best itself (kma_hashindex.hip; KMA_OPT_HASH_CAP). out_stats (optional) = {proteins with at
+ * least one candidate prototype, proteins scored in more than one prototype range, ranges
+ * scored (those holding a candidate)}. The index is read-only after creation: calls on one index may run on several
+ * threads, each call owns its scratch. Fewer than 2^31 prototypes.
+ * KMA_E_INVALID before any device is touched: a null index or output, decreasing offsets, k
+ * outside 2..12, min_sim outside [0, 1).                                                      */
+typedef struct kma_proto_index kma_proto_index;
+struct kma_proto_index_info {
+  uint32_t n_proto;
+  int32_t k;
+  uint64_t n_keys;     /* unique keys */
+  uint64_t n_postings; /* (key, prototype) pairs of distinct keys */
+  uint64_t bytes;      /* device memory the index holds */
+};
+int kma_proto_index_create(const uint8_t* proto_residues, const uint64_t* proto_offsets,
+                           uint32_t n_proto, int k, int device, kma_proto_index** out);
+int kma_proto_index_info(const kma_proto_index* index, struct kma_proto_index_info* out);
+int kma_proto_index_destroy(kma_proto_index* index);
+int kma_hash_annotate_indexed(const kma_proto_index* index, const uint8_t* genome_residues,
+                              const uint64_t* genome_offsets, uint32_t n_genome, double min_sim,
+                              int32_t* out_best, double* out_sim, uint32_t* out_count,
+                              uint64_t* out_stats);
 
 /* ---- signature-table construction (BuildKmerProcessor.java:137-223, RoleCounter.java) -------
  * After role resolution by the host (Feature.getUsefulRoles + the interesting-role filter):

@@ -1,13 +1,15 @@
 // kma_abi_ops.cpp — the projector's one-shot set operators of the C ABI (include/kmeranno.h):
 // peg table, signatures, distances / best match, peg proposals, ORF index, translation,
-// hash-annotate and the sequence MD5 / duplicate check. Each checks its arguments on the host, enters its device, stages its batch in
+// hash-annotate (one-shot and against a resident prototype index) and the sequence MD5 /
+// duplicate check. Each checks its arguments on the host, enters its device, stages its batch in
 // buffers of its own (kma_host.h: upload_batch, Scratch, AlphabetFlag), runs its launchers
-// (kma_proposals.hip, kma_distance.hip, kma_hashanno.hip, kma_orf.hip, kma_translate.hip,
-// kma_md5.hip) on the null stream and copies the results back.
+// (kma_proposals.hip, kma_distance.hip, kma_hashanno.hip, kma_hashindex.hip, kma_orf.hip,
+// kma_translate.hip, kma_md5.hip) on the null stream and copies the results back.
 #include <memory>
 
 #include "kma_distance.h"
 #include "kma_hashanno.h"
+#include "kma_hashindex.h"
 #include "kma_internal.h"
 #include "kma_md5.h"
 #include "kma_objects.h"
@@ -758,6 +760,146 @@ int kma_hash_annotate(const uint8_t* gres, const uint64_t* goff, uint32_t n_gp,
     std::memcpy(&out_sim[i], &bits[i], 8);
     out_best[i] = (int32_t)proto[i];
   }
+  return KMA_OK;
+}
+
+// ---- the resident prototype index (kma_hashindex.hip) ------------------------------------------
+// The prototype side of kma_hash_annotate, built once: ProteinKmers sets as above, then the
+// (key, prototype) pairs of distinct keys sorted by key with the stable radix sort, so that a
+// key's postings ascend by prototype; unique keys and posting starts as the genome side's above.
+int kma_proto_index_create(const uint8_t* pres, const uint64_t* poff, uint32_t n_pt, int k,
+                           int device, kma_proto_index** out) {
+  if (!out) return fail(KMA_E_INVALID, "null argument");
+  *out = nullptr;
+  if (k < 2 || k > 12) return fail(KMA_E_INVALID, "kmer size %d outside 2..12", k);
+  if (int rc = check_side(pres, poff, n_pt, "prototype")) return rc;
+  if (n_pt >= (1u << 31)) return fail(KMA_E_INVALID, "2^31 prototypes or more");
+  std::unique_ptr<kma_proto_index> idx(new kma_proto_index);
+  idx->device = device;
+  idx->k = k;
+  idx->n_proto = n_pt;
+  if (n_pt == 0) return *out = idx.release(), KMA_OK;
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  DevBufs b;
+  AlphabetFlag alpha;
+  uint64_t* d_n;  // [0] pairs, [1] unique keys
+  if (int rc = alpha.init(b)) return rc;
+  KMA_HIP(b.alloc(&d_n, 16));
+  KMA_HIP(hipMemset(d_n, 0, 16));
+  KmerSets p;
+  if (int rc = kmer_sets(b, pres, poff, n_pt, k, alpha.d, p)) return rc;
+  if (int rc = alpha.check()) return rc;
+  const uint64_t pw = std::max<uint64_t>(p.total, 1);
+  uint64_t *pk, *skey, *ukeys;
+  uint32_t *pp, *sproto, *uidx, *ustart;
+  uint8_t* uhead;
+  for (uint64_t** q : {&pk, &skey, &ukeys}) KMA_HIP(b.alloc(q, pw * 8));
+  for (uint32_t** q : {&pp, &sproto, &uidx}) KMA_HIP(b.alloc(q, pw * 4));
+  KMA_HIP(b.alloc(&ustart, (pw + 1) * 4));
+  KMA_HIP(b.alloc(&uhead, pw));
+  Scratch t;
+  KMA_HIP(kma::prim_select_flagged_u64(nullptr, t.ask(), p.sorted, p.first, pk, d_n, p.total, nullptr));
+  KMA_HIP(kma::prim_select_flagged_u32(nullptr, t.ask(), p.owner, p.first, pp, d_n, p.total, nullptr));
+  KMA_HIP(kma::prim_sort_pairs_u64_u32(nullptr, t.ask(), pk, skey, pp, sproto, p.total, 5 * k, nullptr));
+  KMA_HIP(t.alloc(b));
+  KMA_HIP(kma::prim_select_flagged_u64(t.p, t.bytes(), p.sorted, p.first, pk, d_n, p.total, nullptr));
+  KMA_HIP(kma::prim_select_flagged_u32(t.p, t.bytes(), p.owner, p.first, pp, d_n, p.total, nullptr));
+  uint64_t n_pairs = 0, n_u = 0;
+  KMA_HIP(hipMemcpy(&n_pairs, d_n, 8, hipMemcpyDeviceToHost));
+  KMA_HIP(kma::prim_sort_pairs_u64_u32(t.p, t.bytes(), pk, skey, pp, sproto, n_pairs, 5 * k, nullptr));
+  KMA_HIP(kma::launch_run_heads(skey, n_pairs, uhead, uidx, nullptr));
+  KMA_HIP(kma::prim_select_flagged_u64(t.p, t.bytes(), skey, uhead, ukeys, d_n + 1, n_pairs, nullptr));
+  KMA_HIP(kma::prim_select_flagged_u32(t.p, t.bytes(), uidx, uhead, ustart, d_n + 1, n_pairs, nullptr));
+  KMA_HIP(kma::launch_set_end(ustart, d_n + 1, n_pairs, nullptr));
+  KMA_HIP(hipMemcpy(&n_u, d_n + 1, 8, hipMemcpyDeviceToHost));
+  // what stays: exact-size copies (idx frees them on any early return)
+  idx->n_keys = n_u;
+  idx->n_postings = n_pairs;
+  KMA_HIP(hipMalloc(&idx->d_keys, std::max<uint64_t>(n_u, 1) * 8));
+  KMA_HIP(hipMalloc(&idx->d_start, (n_u + 1) * 4));
+  KMA_HIP(hipMalloc(&idx->d_postings, std::max<uint64_t>(n_pairs, 1) * 4));
+  KMA_HIP(hipMalloc(&idx->d_psize, n_pt * 4ull));
+  KMA_HIP(hipMemcpy(idx->d_keys, ukeys, n_u * 8, hipMemcpyDeviceToDevice));
+  KMA_HIP(hipMemcpy(idx->d_start, ustart, (n_u + 1) * 4, hipMemcpyDeviceToDevice));
+  KMA_HIP(hipMemcpy(idx->d_postings, sproto, n_pairs * 4, hipMemcpyDeviceToDevice));
+  KMA_HIP(hipMemcpy(idx->d_psize, p.size, n_pt * 4ull, hipMemcpyDeviceToDevice));
+  KMA_HIP(hipDeviceSynchronize());
+  idx->bytes = n_u * 8 + (n_u + 1) * 4 + n_pairs * 4 + n_pt * 4ull;
+  *out = idx.release();
+  return KMA_OK;
+}
+
+int kma_proto_index_info(const kma_proto_index* idx, struct kma_proto_index_info* out) {
+  if (!idx || !out) return fail(KMA_E_INVALID, "null argument");
+  out->n_proto = idx->n_proto;
+  out->k = idx->k;
+  out->n_keys = idx->n_keys;
+  out->n_postings = idx->n_postings;
+  out->bytes = idx->bytes;
+  return KMA_OK;
+}
+
+int kma_proto_index_destroy(kma_proto_index* idx) {
+  delete idx;
+  return KMA_OK;
+}
+
+int kma_hash_annotate_indexed(const kma_proto_index* idx, const uint8_t* gres,
+                              const uint64_t* goff, uint32_t n_gp, double min_sim,
+                              int32_t* out_best, double* out_sim, uint32_t* out_count,
+                              uint64_t* out_stats) {
+  if (!idx) return fail(KMA_E_INVALID, "null index");
+  if (!(min_sim >= 0.0 && min_sim < 1.0))
+    return fail(KMA_E_INVALID, "Minimum similarity score must be between 0 and 1.");
+  const uint32_t n_pt = idx->n_proto;
+  if ((n_gp && (!out_best || !out_sim)) || (n_pt && !out_count))
+    return fail(KMA_E_INVALID, "null output");
+  if (int rc = check_side(gres, goff, n_gp, "genome protein")) return rc;
+  for (uint32_t i = 0; i < n_gp; ++i) {
+    out_best[i] = -1;
+    out_sim[i] = 0.0;
+  }
+  if (n_pt) std::memset(out_count, 0, n_pt * 4ull);
+  if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = 0;
+  if (n_gp == 0 || n_pt == 0) return KMA_OK;
+  DeviceScope ds(idx->device);
+  if (int rc = ds.entered()) return rc;
+  DevBufs b;  // the call's scratch: nothing of the index is written
+  AlphabetFlag alpha;
+  if (int rc = alpha.init(b)) return rc;
+  KmerSets g;
+  if (int rc = kmer_sets(b, gres, goff, n_gp, idx->k, alpha.d, g)) return rc;
+  if (int rc = alpha.check()) return rc;
+  kma::HashIndexArgs a{};
+  a.ukeys = idx->d_keys;
+  a.pstart = idx->d_start;
+  a.postings = idx->d_postings;
+  a.psize = idx->d_psize;
+  a.n_u = idx->n_keys;
+  a.n_proto = n_pt;
+  a.gsorted = g.sorted;
+  a.gfirst = g.first;
+  a.goff = g.off;
+  a.gsize = g.size;
+  a.n_gpos = g.total;
+  a.n_genome = n_gp;
+  a.min_sim = min_sim;
+  const int64_t cap = opt(KMA_OPT_HASH_CAP);
+  a.cap = cap > 0 ? (uint32_t)cap : kma::kHashCapDefault;
+  KMA_HIP(b.alloc(&a.gmatch, std::max<uint64_t>(g.total, 1) * 4));
+  KMA_HIP(b.alloc(&a.out_count, n_pt * 4ull));
+  KMA_HIP(b.alloc(&a.out_best, n_gp * 4ull));
+  KMA_HIP(b.alloc(&a.out_sim, n_gp * 8ull));
+  KMA_HIP(b.alloc(&a.stats, 24));
+  KMA_HIP(hipMemset(a.out_count, 0, n_pt * 4ull));
+  KMA_HIP(hipMemset(a.stats, 0, 24));
+  KMA_HIP(kma::launch_index_lookup(a, nullptr));
+  KMA_HIP(kma::launch_index_score(a, nullptr));
+  KMA_HIP(hipMemcpy(out_best, a.out_best, n_gp * 4ull, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_sim, a.out_sim, n_gp * 8ull, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_count, a.out_count, n_pt * 4ull, hipMemcpyDeviceToHost));
+  if (out_stats) KMA_HIP(hipMemcpy(out_stats, a.stats, 24, hipMemcpyDeviceToHost));
   return KMA_OK;
 }
 

@@ -20,8 +20,9 @@ namespace host {
 // environment is read only by tuning builds (-DKMA_TUNING_ENV=1, the A/B scripts' variants):
 // a library a JVM loads must not change its kernel geometry because of a stray variable.
 namespace {
-constexpr int kNumOpts = 11;
-std::atomic<int64_t> g_opt[kNumOpts] = {{0}, {-1}, {0}, {-1}, {0}, {0}, {1}, {0}, {0}, {-1}, {0}};
+constexpr int kNumOpts = 13;  // (number 11 is no option: include/kmeranno.h)
+std::atomic<int64_t> g_opt[kNumOpts] = {{0}, {-1}, {0}, {-1}, {0}, {0}, {1}, {0},
+                                         {0}, {-1}, {0}, {0}, {0}};
 }  // namespace
 
 bool option_valid(int opt, int64_t v) {
@@ -36,6 +37,7 @@ bool option_valid(int opt, int64_t v) {
     case KMA_OPT_HOST_SLICE: return v >= 0 && v <= (int64_t)((1ull << 32) - 128);  // a call's limit
     case KMA_OPT_HOST_PIECE_MIN: return v >= 0 && v <= (int64_t)(1ull << 32);
     case KMA_OPT_PLACEMENT: return v >= -1 && v <= 1;
+    case KMA_OPT_HASH_CAP: return v >= 0 && v <= 2048;  // kma_hashindex.h kHashCapMax
     default: return false;
   }
 }
@@ -261,7 +263,7 @@ int kma_option_set(int option, int64_t value) {
 }
 
 int kma_option_get(int option, int64_t* value) {
-  if (!value || option < 1 || option >= kNumOpts)
+  if (!value || option < 1 || option >= kNumOpts || option == 11)
     return fail(KMA_E_INVALID, "option %d unknown (or null value)", option);
   *value = opt(option);
   return KMA_OK;

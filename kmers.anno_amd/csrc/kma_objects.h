@@ -1,5 +1,5 @@
-// kma_objects.h — the objects behind the C ABI's opaque handles (kma_workspace, kma_table), a
-// table's replicas and host-context pool, and the phase clock of timed device calls. Shared by
+// kma_objects.h — the objects behind the C ABI's opaque handles (kma_workspace, kma_table,
+// kma_proto_index), a table's replicas and host-context pool, and the phase clock of timed device calls. Shared by
 // the kma_abi_*.cpp units; private to the library, not installed.
 #pragma once
 #include "kma_host.h"
@@ -85,6 +85,26 @@ struct kma_table {
   mutable std::mutex reps_mu;
   std::mutex pool_mu;
   std::vector<kma::host::HostCtx*> idle;  // host contexts not in use
+};
+
+// The hash annotator's resident prototype index (kma_hashindex.h): read-only after
+// kma_proto_index_create, so calls may share it across threads; each call owns its scratch.
+struct kma_proto_index {
+  int device = 0;
+  int k = 8;
+  uint32_t n_proto = 0;
+  uint64_t n_keys = 0, n_postings = 0, bytes = 0;
+  uint64_t* d_keys = nullptr;      // n_keys sorted unique window keys
+  uint32_t* d_start = nullptr;     // n_keys + 1 posting starts
+  uint32_t* d_postings = nullptr;  // n_postings prototypes, ascending per key
+  uint32_t* d_psize = nullptr;     // distinct kmers per prototype
+  kma_proto_index() = default;
+  kma_proto_index(const kma_proto_index&) = delete;
+  kma_proto_index& operator=(const kma_proto_index&) = delete;
+  ~kma_proto_index() {
+    for (void* q : {(void*)d_keys, (void*)d_start, (void*)d_postings, (void*)d_psize})
+      if (q) (void)hipFree(q);
+  }
 };
 
 namespace kma {

@@ -48,15 +48,17 @@ EXPORTS = (
     "kma_orf_index_create", "kma_orf_index_destroy", "kma_extend_proposals",
     "kma_translate_locations",
     "kma_sequence_md5_device", "kma_sequence_md5", "kma_check_sequences",
+    "kma_proto_index_create", "kma_proto_index_info", "kma_proto_index_destroy",
+    "kma_hash_annotate_indexed",
 )
 
 # Tuning options (include/kmeranno.h "options"): library-wide defaults read per call.
 OPT_LAYOUT, OPT_BLOCK_PROTEINS, OPT_DEFER, OPT_HOST_PIECES, OPT_HASH_SLICE = 1, 2, 3, 4, 5
 OPT_PACKED_INPUT, OPT_HOST_THREADS, OPT_HOST_SLICE, OPT_PLACEMENT = 6, 7, 8, 9
-OPT_HOST_PIECE_MIN = 10
+OPT_HOST_PIECE_MIN, OPT_HASH_CAP = 10, 12  # (11 is no option)
 OPT_DEFAULTS = {OPT_LAYOUT: -1, OPT_BLOCK_PROTEINS: 0, OPT_DEFER: -1, OPT_HOST_PIECES: 0,
                 OPT_HASH_SLICE: 0, OPT_PACKED_INPUT: 1, OPT_HOST_THREADS: 0, OPT_HOST_SLICE: 0,
-                OPT_PLACEMENT: -1, OPT_HOST_PIECE_MIN: 0}
+                OPT_PLACEMENT: -1, OPT_HOST_PIECE_MIN: 0, OPT_HASH_CAP: 0}
 LAYOUT_TWO_CHOICE = 0x100  # layout code flag: two-choice placement (include/kmeranno.h)
 LAYOUT_MOD_SAMPLING = 0x40  # layout code flag: the mod-sampling minimizer order (K = 8, m = 6)
 OPT_DEFAULT = -(1 << 63)  # kma_workspace_option_set: follow the library default
@@ -64,7 +66,7 @@ _OPT_NAMES = {"layout": OPT_LAYOUT, "block_proteins": OPT_BLOCK_PROTEINS, "defer
               "host_pieces": OPT_HOST_PIECES, "hash_slice": OPT_HASH_SLICE,
               "packed_input": OPT_PACKED_INPUT, "host_threads": OPT_HOST_THREADS,
               "host_slice": OPT_HOST_SLICE, "placement": OPT_PLACEMENT,
-              "host_piece_min": OPT_HOST_PIECE_MIN}
+              "host_piece_min": OPT_HOST_PIECE_MIN, "hash_cap": OPT_HASH_CAP}
 
 
 class KmerAnnoError(RuntimeError):
@@ -83,6 +85,11 @@ class TableInfo(C.Structure):
                 ("replicate_bytes", C.c_uint64), ("two_choice", C.c_int32),
                 ("minimizer_order", C.c_int32), ("replicate_peer", C.c_int32),
                 ("replicate_local", C.c_int32)]
+
+
+class ProtoIndexInfo(C.Structure):
+    _fields_ = [("n_proto", C.c_uint32), ("k", C.c_int32), ("n_keys", C.c_uint64),
+                ("n_postings", C.c_uint64), ("bytes", C.c_uint64)]
 
 
 HIT_DTYPE = np.dtype([("contig", "<u4"), ("left", "<i4"), ("fid", "<u4"), ("strand", "u1"),
@@ -180,6 +187,11 @@ def load(path: str | None = None):
         L.kma_sequence_md5.argtypes = [_vp, _vp, _u32, _u32, _int, _vp]
         L.kma_check_sequences.argtypes = [_vp, _vp, _u32, _u32, _vp, _int, _vp, _vp, _vp, _vp,
                                           _vp]
+        L.kma_proto_index_create.argtypes = [_vp, _vp, _u32, _int, _int, C.POINTER(_vp)]
+        L.kma_proto_index_info.argtypes = [_vp, C.POINTER(ProtoIndexInfo)]
+        L.kma_proto_index_destroy.argtypes = [_vp]
+        L.kma_hash_annotate_indexed.argtypes = [_vp, _vp, _vp, _u32, C.c_double, _vp, _vp, _vp,
+                                                _vp]
         L.kma_debug_translate_ms.restype = C.c_double
         L.kma_debug_translate_ms.argtypes = []
         L.kma_contig_window_count.restype = _u64
@@ -219,7 +231,7 @@ def reset_options():
 
 @contextlib.contextmanager
 def options(**kw):
-    """Set options by name (layout=, block_proteins=, defer=, host_pieces=, hash_slice=) for
+    """Set options by name (layout=, block_proteins=, defer=, host_pieces=, hash_slice=, ...) for
     the body, then restore the previous values."""
     old = {_OPT_NAMES[k]: get_option(_OPT_NAMES[k]) for k in kw}
     try:
@@ -845,6 +857,75 @@ def hash_annotate(genome_residues, genome_offsets, proto_residues, proto_offsets
                                     min_sim, device, best.ctypes.data, sim.ctypes.data,
                                     cnt.ctypes.data))
     return best[:n_g], sim[:n_g], cnt[:n_p]
+
+
+class ProtoIndex:
+    """kma_proto_index: the prototypes of a role annotation file resident on one GPU (their
+    sorted unique K-mer keys, postings and set sizes), built once and scored against genome
+    after genome with hash_annotate_indexed. Read-only after creation; a context manager."""
+
+    def __init__(self, proto_residues, proto_offsets, k: int = 8, device: int = 0):
+        pr = np.ascontiguousarray(proto_residues, np.uint8)
+        po = np.ascontiguousarray(proto_offsets, np.uint64)
+        self._h = _vp()
+        if not len(pr):
+            pr = np.zeros(1, np.uint8)
+        _check(load().kma_proto_index_create(pr.ctypes.data,
+                                             po.ctypes.data, len(po) - 1, k, device,
+                                             C.byref(self._h)))
+
+    @classmethod
+    def from_strings(cls, proteins, k: int = 8, device: int = 0):
+        return cls(*pack_strings(proteins), k=k, device=device)
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise KmerAnnoError(E_INVALID, "the prototype index is closed")
+        return self._h
+
+    def info(self) -> ProtoIndexInfo:
+        out = ProtoIndexInfo()
+        _check(load().kma_proto_index_info(self.handle, C.byref(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            load().kma_proto_index_destroy(self._h)
+            self._h = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def hash_annotate_indexed(index: ProtoIndex, genome_residues, genome_offsets,
+                          min_sim: float = 0.0125, stats: bool = False):
+    """kma_hash_annotate_indexed: hash_annotate's three results for one genome against a
+    resident ProtoIndex (its K and device); with stats, also [proteins with a candidate,
+    proteins scored in more than one prototype range, ranges scored]."""
+    gr = np.ascontiguousarray(genome_residues, np.uint8)
+    go = np.ascontiguousarray(genome_offsets, np.uint64)
+    n_g, n_p = len(go) - 1, index.info().n_proto
+    best = np.empty(max(n_g, 1), np.int32)
+    sim = np.empty(max(n_g, 1), np.float64)
+    cnt = np.empty(max(n_p, 1), np.uint32)
+    st = np.zeros(3, np.uint64)
+    if not len(gr):
+        gr = np.zeros(1, np.uint8)
+    _check(load().kma_hash_annotate_indexed(index.handle, gr.ctypes.data,
+                                            go.ctypes.data, n_g, min_sim, best.ctypes.data,
+                                            sim.ctypes.data, cnt.ctypes.data, st.ctypes.data))
+    out = (best[:n_g], sim[:n_g], cnt[:n_p])
+    return out + (st,) if stats else out
 
 
 def build_signatures(residues: np.ndarray, offsets: np.ndarray, roles, k: int = 8,
