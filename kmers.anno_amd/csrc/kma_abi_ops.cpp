@@ -1,15 +1,11 @@
-// kma_abi_ops.cpp — the projector's one-shot set operators of the C ABI (include/kmeranno.h):
-// peg table, signatures, distances / best match, peg proposals, ORF index, translation,
-// hash-annotate (one-shot and against a resident prototype index) and the sequence MD5 /
-// duplicate check. Each checks its arguments on the host, enters its device, stages its batch in
-// buffers of its own (kma_host.h: upload_batch, Scratch, AlphabetFlag), runs its launchers
-// (kma_proposals.hip, kma_distance.hip, kma_hashanno.hip, kma_hashindex.hip, kma_orf.hip,
-// kma_translate.hip, kma_md5.hip) on the null stream and copies the results back.
+// kma_abi_ops.cpp — the projector's one-shot operators of the C ABI (include/kmeranno.h) that
+// build no ProteinKmers sets (those are in kma_abi_sets.cpp): peg table, signatures, peg
+// proposals, ORF index, translation and the sequence MD5 / duplicate check. Each checks its
+// arguments on the host, enters its device, stages its batch in buffers of its own (kma_host.h:
+// upload_batch, Scratch, AlphabetFlag), runs its launchers (kma_build.hip, kma_proposals.hip,
+// kma_orf.hip, kma_translate.hip, kma_md5.hip) on the null stream and copies the results back.
 #include <memory>
 
-#include "kma_distance.h"
-#include "kma_hashanno.h"
-#include "kma_hashindex.h"
 #include "kma_internal.h"
 #include "kma_md5.h"
 #include "kma_objects.h"
@@ -150,108 +146,6 @@ int kma_build_signatures(const uint8_t* residues, const uint64_t* offsets, const
   if (n_sel == 0) return KMA_OK;
   KMA_HIP(hipMemcpy(out_keys, d_ka, n_sel * 8, hipMemcpyDeviceToHost));
   KMA_HIP(hipMemcpy(out_roles, d_ta, n_sel * 4, hipMemcpyDeviceToHost));
-  return KMA_OK;
-}
-
-// ---- ProteinKmers.distance (GeneCopyProcessor.java:129-162) ------------------------------------
-int kma_protein_distances(const uint8_t* residues, const uint64_t* offsets, uint32_t n_seq, int k,
-                          uint32_t flags, const uint32_t* pair_a, const uint32_t* pair_b,
-                          uint64_t n_pairs, int device, uint32_t* out_sim, uint32_t* out_size,
-                          double* out_dist) {
-  if (k < 2 || k > 12) return fail(KMA_E_INVALID, "kmer size %d outside 2..12", k);
-  if (flags & ~KMA_F_END_EXCLUSIVE) return fail(KMA_E_INVALID, "bad flags");
-  if (n_pairs && (!pair_a || !pair_b || !out_sim)) return fail(KMA_E_INVALID, "null argument");
-  if (n_seq && (!residues || !offsets)) return fail(KMA_E_INVALID, "null argument");
-  for (uint64_t i = 0; i < n_pairs; ++i)
-    if (pair_a[i] >= n_seq || pair_b[i] >= n_seq)
-      return fail(KMA_E_INVALID, "pair %llu indexes a protein >= %u", (unsigned long long)i,
-                  n_seq);
-  if (int rc = check_offsets(offsets, n_seq, "", 1ull << 31,
-                             "more than 2^31 residues in one call"))
-    return rc;
-  if (n_seq == 0 || (n_pairs == 0 && !out_size)) return KMA_OK;
-  DeviceScope ds(device);
-  if (int rc = ds.entered()) return rc;
-  DevBufs b;
-  DevBatch in;
-  if (int rc = upload_batch(b, residues, offsets, n_seq, 64, &in)) return rc;
-  uint64_t *d_off = in.off, *d_keys, *d_sorted;
-  uint32_t *d_size, *d_pa, *d_pb, *d_sim;
-  const uint64_t total = in.total;
-  const uint64_t nw = std::max<uint64_t>(total, 1), np = std::max<uint64_t>(n_pairs, 1);
-  KMA_HIP(b.alloc(&d_keys, nw * 8));
-  KMA_HIP(b.alloc(&d_sorted, nw * 8));
-  KMA_HIP(b.alloc(&d_size, n_seq * 4ull));
-  KMA_HIP(b.alloc(&d_pa, np * 4));
-  KMA_HIP(b.alloc(&d_pb, np * 4));
-  KMA_HIP(b.alloc(&d_sim, np * 4));
-  if (n_pairs) {
-    KMA_HIP(hipMemcpy(d_pa, pair_a, n_pairs * 4, hipMemcpyHostToDevice));
-    KMA_HIP(hipMemcpy(d_pb, pair_b, n_pairs * 4, hipMemcpyHostToDevice));
-  }
-  AlphabetFlag alpha;
-  if (int rc = alpha.init(b)) return rc;
-  KMA_HIP(kma::launch_window_keys(in.bytes, d_off, n_seq, k,
-                                  (flags & KMA_F_END_EXCLUSIVE) ? 1 : 0, d_keys, alpha.d, nullptr));
-  Scratch tmp;
-  KMA_HIP(kma::launch_segmented_sort(nullptr, tmp.ask(), d_keys, d_sorted, total, n_seq, d_off,
-                                     d_off + 1, 5 * k, nullptr));
-  KMA_HIP(tmp.alloc(b));
-  KMA_HIP(kma::launch_segmented_sort(tmp.p, tmp.bytes(), d_keys, d_sorted, total, n_seq, d_off,
-                                     d_off + 1, 5 * k, nullptr));
-  KMA_HIP(kma::launch_distinct(d_sorted, d_off, n_seq, d_size, nullptr));
-  if (n_pairs)
-    KMA_HIP(kma::launch_pairs(d_sorted, d_off, d_size, d_sorted, d_off, d_size, d_pa, d_pb,
-                              n_pairs, d_sim, nullptr));
-  if (int rc = alpha.check()) return rc;
-  std::vector<uint32_t> size(n_seq);
-  KMA_HIP(hipMemcpy(size.data(), d_size, n_seq * 4ull, hipMemcpyDeviceToHost));
-  if (out_size) std::memcpy(out_size, size.data(), n_seq * 4ull);
-  if (n_pairs) KMA_HIP(hipMemcpy(out_sim, d_sim, n_pairs * 4, hipMemcpyDeviceToHost));
-  if (out_dist)
-    for (uint64_t i = 0; i < n_pairs; ++i) {
-      // SequenceKmers.distance restated: 1 - similarity / union, 1.0 when nothing is shared
-      const uint32_t sim = out_sim[i];
-      const double uni = (double)size[pair_a[i]] + (double)size[pair_b[i]] - (double)sim;
-      out_dist[i] = sim > 0 ? 1.0 - (double)sim / uni : 1.0;
-    }
-  return KMA_OK;
-}
-
-int kma_protein_best_match(const uint8_t* residues, const uint64_t* offsets, uint32_t n_seq, int k,
-                           uint32_t flags, const uint32_t* query, const uint64_t* cand_off,
-                           const uint32_t* cand, uint32_t n_query, double max_dist, int device,
-                           int32_t* out_best, double* out_best_dist) {
-  if (n_query && (!query || !cand_off || !out_best)) return fail(KMA_E_INVALID, "null argument");
-  const uint64_t n_pairs = n_query ? cand_off[n_query] - cand_off[0] : 0;
-  if (n_pairs && !cand) return fail(KMA_E_INVALID, "null argument");
-  for (uint32_t q = 0; q < n_query; ++q)
-    if (cand_off[q + 1] < cand_off[q]) return fail(KMA_E_INVALID, "cand_off decreases at %u", q);
-  std::vector<uint32_t> pa(n_pairs), pb(n_pairs), sim(n_pairs);
-  std::vector<double> dist(n_pairs);
-  for (uint32_t q = 0; q < n_query; ++q)
-    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) {
-      pa[i - cand_off[0]] = query[q];
-      pb[i - cand_off[0]] = cand[i];
-    }
-  if (int rc = kma_protein_distances(residues, offsets, n_seq, k, flags, pa.data(), pb.data(),
-                                     n_pairs, device, sim.data(), nullptr, dist.data()))
-    return rc;
-  // GeneCopyProcessor.java:135-146: fDist = maxDist; for each candidate in order,
-  // if (f2Dist <= fDist) { fDist = f2Dist; found = f2; }
-  for (uint32_t q = 0; q < n_query; ++q) {
-    double best = max_dist;
-    int32_t found = -1;
-    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) {
-      const double d = dist[i - cand_off[0]];
-      if (d <= best) {
-        best = d;
-        found = (int32_t)cand[i];
-      }
-    }
-    out_best[q] = found;
-    if (out_best_dist) out_best_dist[q] = best;
-  }
   return KMA_OK;
 }
 
@@ -551,357 +445,6 @@ int kma_translate_locations(const uint8_t* dna, const uint64_t* offsets, uint32_
 // Not in kmeranno.h: measurement hook. hipEvent time of the kernel of this thread's last
 // kma_translate_locations call (0 when it launched none).
 double kma_debug_translate_ms(void) { return g_translate_kernel_ms; }
-
-}  // extern "C"
-
-namespace {
-// Window keys, per-protein sort and distinct sizes of a batch (device buffers in b): the
-// ProteinKmers sets of kma_hash_annotate's two sides.
-struct KmerSets {
-  uint8_t* res = nullptr;
-  uint64_t* off = nullptr;
-  uint64_t *keys = nullptr, *sorted = nullptr;
-  uint32_t *size = nullptr, *owner = nullptr;
-  uint8_t* first = nullptr;
-  uint64_t total = 0;
-};
-
-int kmer_sets(DevBufs& b, const uint8_t* residues, const uint64_t* offsets, uint32_t n, int k,
-              uint32_t* d_alpha, KmerSets& ks) {
-  DevBatch in;
-  if (int rc = upload_batch(b, residues, offsets, n, 64, &in)) return rc;
-  ks.res = in.bytes, ks.off = in.off, ks.total = in.total;
-  const uint64_t nw = std::max<uint64_t>(ks.total, 1);
-  KMA_HIP(b.alloc(&ks.keys, nw * 8));
-  KMA_HIP(b.alloc(&ks.sorted, nw * 8));
-  KMA_HIP(b.alloc(&ks.size, std::max<uint64_t>(n, 1) * 4));
-  KMA_HIP(b.alloc(&ks.owner, nw * 4));
-  KMA_HIP(b.alloc(&ks.first, nw));
-  KMA_HIP(kma::launch_window_keys(ks.res, ks.off, n, k, 0, ks.keys, d_alpha, nullptr));
-  Scratch tmp;
-  KMA_HIP(kma::launch_segmented_sort(nullptr, tmp.ask(), ks.keys, ks.sorted, ks.total, n, ks.off,
-                                     ks.off + 1, 5 * k, nullptr));
-  KMA_HIP(tmp.alloc(b));
-  KMA_HIP(kma::launch_segmented_sort(tmp.p, tmp.bytes(), ks.keys, ks.sorted, ks.total, n, ks.off,
-                                     ks.off + 1, 5 * k, nullptr));
-  KMA_HIP(kma::launch_distinct(ks.sorted, ks.off, n, ks.size, nullptr));
-  KMA_HIP(kma::launch_owner_first(ks.sorted, ks.off, n, ks.owner, ks.first, nullptr));
-  return KMA_OK;
-}
-
-// One side of kma_hash_annotate (`what` names it in the messages).
-int check_side(const uint8_t* residues, const uint64_t* offsets, uint32_t n, const char* what) {
-  if (n && (!residues || !offsets)) return fail(KMA_E_INVALID, "null %s", what);
-  const std::string too_long = std::string("more than 2^31 ") + what + " residues";
-  return check_offsets(offsets, n, what, 1ull << 31, too_long.c_str());
-}
-}  // namespace
-
-extern "C" {
-
-int kma_hash_annotate(const uint8_t* gres, const uint64_t* goff, uint32_t n_gp,
-                      const uint8_t* pres, const uint64_t* poff, uint32_t n_pt, int k,
-                      double min_sim, int device, int32_t* out_best, double* out_sim,
-                      uint32_t* out_count) {
-  if (k < 2 || k > 12) return fail(KMA_E_INVALID, "kmer size %d outside 2..12", k);
-  if (!(min_sim >= 0.0 && min_sim < 1.0))
-    return fail(KMA_E_INVALID, "Minimum similarity score must be between 0 and 1.");
-  if ((n_gp && (!out_best || !out_sim)) || (n_pt && !out_count))
-    return fail(KMA_E_INVALID, "null output");
-  if (int rc = check_side(gres, goff, n_gp, "genome protein")) return rc;
-  if (int rc = check_side(pres, poff, n_pt, "prototype")) return rc;
-  for (uint32_t i = 0; i < n_gp; ++i) {
-    out_best[i] = -1;
-    out_sim[i] = 0.0;
-  }
-  if (n_pt) std::memset(out_count, 0, n_pt * 4ull);
-  if (n_gp == 0 || n_pt == 0) return KMA_OK;
-  DeviceScope ds(device);
-  if (int rc = ds.entered()) return rc;
-  DevBufs b;
-  AlphabetFlag alpha;
-  uint64_t* d_n;  // [0] genome pairs, [1] unique keys, [2] runs
-  if (int rc = alpha.init(b)) return rc;
-  KMA_HIP(b.alloc(&d_n, 32));
-  KMA_HIP(hipMemset(d_n, 0, 32));
-  KmerSets g, p;
-  if (int rc = kmer_sets(b, gres, goff, n_gp, k, alpha.d, g)) return rc;
-  if (int rc = kmer_sets(b, pres, poff, n_pt, k, alpha.d, p)) return rc;
-  if (int rc = alpha.check()) return rc;
-  const int kb = 5 * k;
-  // genome (key, protein) pairs of distinct keys, sorted by key; unique keys and ranges
-  const uint64_t gw = std::max<uint64_t>(g.total, 1);
-  uint64_t *gpk, *skey, *ukeys;
-  uint32_t *gpp, *sprot, *uidx, *ustart;
-  uint8_t* uhead;
-  for (uint64_t** q : {&gpk, &skey, &ukeys}) KMA_HIP(b.alloc(q, gw * 8));
-  for (uint32_t** q : {&gpp, &sprot, &uidx}) KMA_HIP(b.alloc(q, gw * 4));
-  KMA_HIP(b.alloc(&ustart, (gw + 1) * 4));
-  KMA_HIP(b.alloc(&uhead, gw));
-  Scratch t1;
-  KMA_HIP(kma::prim_select_flagged_u64(nullptr, t1.ask(), g.sorted, g.first, gpk, d_n, g.total, nullptr));
-  KMA_HIP(kma::prim_select_flagged_u32(nullptr, t1.ask(), g.owner, g.first, gpp, d_n, g.total, nullptr));
-  KMA_HIP(kma::prim_sort_pairs_u64_u32(nullptr, t1.ask(), gpk, skey, gpp, sprot, g.total, kb, nullptr));
-  KMA_HIP(kma::prim_excl_sum_u32_u64(nullptr, t1.ask(), nullptr, nullptr, std::max<uint64_t>(p.total, 1), nullptr));
-  KMA_HIP(t1.alloc(b));
-  KMA_HIP(kma::prim_select_flagged_u64(t1.p, t1.bytes(), g.sorted, g.first, gpk, d_n, g.total, nullptr));
-  KMA_HIP(kma::prim_select_flagged_u32(t1.p, t1.bytes(), g.owner, g.first, gpp, d_n, g.total, nullptr));
-  uint64_t n_pairs = 0;
-  KMA_HIP(hipMemcpy(&n_pairs, d_n, 8, hipMemcpyDeviceToHost));
-  KMA_HIP(kma::prim_sort_pairs_u64_u32(t1.p, t1.bytes(), gpk, skey, gpp, sprot, n_pairs, kb, nullptr));
-  KMA_HIP(kma::launch_run_heads(skey, n_pairs, uhead, uidx, nullptr));
-  KMA_HIP(kma::prim_select_flagged_u64(t1.p, t1.bytes(), skey, uhead, ukeys, d_n + 1, n_pairs, nullptr));
-  KMA_HIP(kma::prim_select_flagged_u32(t1.p, t1.bytes(), uidx, uhead, ustart, d_n + 1, n_pairs, nullptr));
-  KMA_HIP(kma::launch_set_end(ustart, d_n + 1, n_pairs, nullptr));
-  // candidates: one (prototype, protein) per shared distinct key
-  kma::HashArgs a{};
-  a.n_ppos = p.total;
-  a.pfirst = p.first;
-  a.psorted = p.sorted;
-  a.powner = p.owner;
-  a.psize = p.size;
-  a.ukeys = ukeys;
-  a.n_u = d_n + 1;
-  a.ustart = ustart;
-  a.gprot = sprot;
-  a.gsize = g.size;
-  a.min_sim = min_sim;
-  const uint64_t pw = std::max<uint64_t>(p.total, 1);
-  uint64_t* coff;
-  KMA_HIP(b.alloc(&a.ccount, pw * 4));
-  KMA_HIP(b.alloc(&a.cu, pw * 4));
-  KMA_HIP(b.alloc(&coff, pw * 8));
-  a.coff = coff;
-  KMA_HIP(kma::launch_cand_count(a, nullptr));
-  KMA_HIP(kma::prim_excl_sum_u32_u64(t1.p, t1.bytes(), a.ccount, coff, p.total, nullptr));
-  uint64_t last_off = 0;
-  uint32_t last_cnt = 0;
-  if (p.total) {
-    KMA_HIP(hipMemcpy(&last_off, coff + p.total - 1, 8, hipMemcpyDeviceToHost));
-    KMA_HIP(hipMemcpy(&last_cnt, a.ccount + p.total - 1, 4, hipMemcpyDeviceToHost));
-  }
-  const uint64_t n_cand = last_off + last_cnt;
-  KMA_HIP(b.alloc(&a.out_count, n_pt * 4ull));
-  uint64_t* best_bits;
-  uint32_t* best_proto;
-  KMA_HIP(b.alloc(&best_bits, n_gp * 8ull));
-  KMA_HIP(b.alloc(&best_proto, n_gp * 4ull));
-  KMA_HIP(b.alloc(&a.best_bits, n_gp * 8ull));
-  KMA_HIP(b.alloc(&a.best_proto, n_gp * 4ull));
-  KMA_HIP(hipMemset(a.out_count, 0, n_pt * 4ull));
-  for (uint64_t* q : {best_bits, a.best_bits}) KMA_HIP(hipMemset(q, 0, n_gp * 8ull));
-  for (uint32_t* q : {best_proto, a.best_proto}) KMA_HIP(hipMemset(q, 0xFF, n_gp * 4ull));
-  // Candidates are scored in slices of whole prototypes (file order) whose sort and run-length
-  // encoding stay below 2^31 elements (the int counts of the CUB-style APIs this was first written against; rocPRIM's select and sort take size_t, its run-length encode still unsigned); a slice's best per protein
-  // replaces the running best only when strictly higher, so earlier prototypes keep ties.
-  // KMA_OPT_HASH_SLICE (tests) lowers the slice size.
-  uint64_t slice_cap = (1ull << 31) - 1;
-  if (const int64_t o = opt(KMA_OPT_HASH_SLICE); o > 0)
-    slice_cap = std::min<uint64_t>(slice_cap, (uint64_t)o);
-  std::vector<uint64_t> cum(n_pt + 1, 0);
-  if (n_cand) {
-    uint64_t* d_cum;
-    KMA_HIP(b.alloc(&d_cum, (n_pt + 1) * 8ull));
-    KMA_HIP(kma::launch_proto_cum(coff, a.ccount, p.off, n_pt, p.total, d_cum, nullptr));
-    KMA_HIP(hipMemcpy(cum.data(), d_cum, (n_pt + 1) * 8ull, hipMemcpyDeviceToHost));
-  }
-  std::vector<uint32_t> cut{0};  // slice boundaries in prototypes
-  for (uint32_t q = 0; q < n_pt; ++q) {
-    if (cum[q + 1] - cum[q] > (1ull << 31) - 1)
-      return fail(KMA_E_CAPACITY, "prototype %u has %llu candidates (limit 2^31 - 1)", q,
-                  (unsigned long long)(cum[q + 1] - cum[q]));
-    if (q > cut.back() && cum[q + 1] - cum[cut.back()] > slice_cap) cut.push_back(q);
-  }
-  cut.push_back(n_pt);
-  uint64_t max_slice = 0;
-  for (size_t i = 0; i + 1 < cut.size(); ++i)
-    max_slice = std::max(max_slice, cum[cut[i + 1]] - cum[cut[i]]);
-  if (max_slice) {
-    uint64_t *cand, *csorted, *runs;
-    uint32_t* run_len;
-    KMA_HIP(b.alloc(&cand, max_slice * 8));
-    KMA_HIP(b.alloc(&csorted, max_slice * 8));
-    KMA_HIP(b.alloc(&runs, max_slice * 8));
-    KMA_HIP(b.alloc(&run_len, max_slice * 4));
-    int pbits = 1;
-    while (pbits < 32 && (1ull << pbits) < n_pt) ++pbits;
-    Scratch t2;
-    KMA_HIP(kma::prim_sort_keys_u64(nullptr, t2.ask(), cand, csorted, max_slice, 32 + pbits, nullptr));
-    KMA_HIP(kma::prim_rle_u64(nullptr, t2.ask(), csorted, runs, run_len, d_n + 2, max_slice, nullptr));
-    KMA_HIP(t2.alloc(b));
-    std::vector<uint64_t> hoff(n_pt + 1);
-    KMA_HIP(hipMemcpy(hoff.data(), p.off, (n_pt + 1) * 8ull, hipMemcpyDeviceToHost));
-    a.cand = cand;
-    a.runs = runs;
-    a.run_len = run_len;
-    a.n_runs = d_n + 2;
-    for (size_t i = 0; i + 1 < cut.size(); ++i) {
-      const uint64_t nc = cum[cut[i + 1]] - cum[cut[i]];
-      if (!nc) continue;
-      a.pos_lo = hoff[cut[i]] - hoff[0];
-      a.pos_hi = hoff[cut[i + 1]] - hoff[0];
-      a.cand_base = cum[cut[i]];
-      KMA_HIP(kma::launch_cand_emit(a, nullptr));
-      KMA_HIP(kma::prim_sort_keys_u64(t2.p, t2.bytes(), cand, csorted, nc, 32 + pbits, nullptr));
-      KMA_HIP(kma::prim_rle_u64(t2.p, t2.bytes(), csorted, runs, run_len, d_n + 2, nc, nullptr));
-      KMA_HIP(kma::launch_score(a, nc, nullptr));
-      KMA_HIP(kma::launch_choose(a, nc, nullptr));
-      KMA_HIP(kma::launch_merge_best(best_bits, best_proto, a.best_bits, a.best_proto, n_gp,
-                                     nullptr));
-    }
-  }
-  std::vector<uint64_t> bits(n_gp);
-  std::vector<uint32_t> proto(n_gp);
-  KMA_HIP(hipMemcpy(bits.data(), best_bits, n_gp * 8ull, hipMemcpyDeviceToHost));
-  KMA_HIP(hipMemcpy(proto.data(), best_proto, n_gp * 4ull, hipMemcpyDeviceToHost));
-  KMA_HIP(hipMemcpy(out_count, a.out_count, n_pt * 4ull, hipMemcpyDeviceToHost));
-  for (uint32_t i = 0; i < n_gp; ++i) {
-    if (proto[i] == 0xFFFFFFFFu) continue;
-    std::memcpy(&out_sim[i], &bits[i], 8);
-    out_best[i] = (int32_t)proto[i];
-  }
-  return KMA_OK;
-}
-
-// ---- the resident prototype index (kma_hashindex.hip) ------------------------------------------
-// The prototype side of kma_hash_annotate, built once: ProteinKmers sets as above, then the
-// (key, prototype) pairs of distinct keys sorted by key with the stable radix sort, so that a
-// key's postings ascend by prototype; unique keys and posting starts as the genome side's above.
-int kma_proto_index_create(const uint8_t* pres, const uint64_t* poff, uint32_t n_pt, int k,
-                           int device, kma_proto_index** out) {
-  if (!out) return fail(KMA_E_INVALID, "null argument");
-  *out = nullptr;
-  if (k < 2 || k > 12) return fail(KMA_E_INVALID, "kmer size %d outside 2..12", k);
-  if (int rc = check_side(pres, poff, n_pt, "prototype")) return rc;
-  if (n_pt >= (1u << 31)) return fail(KMA_E_INVALID, "2^31 prototypes or more");
-  std::unique_ptr<kma_proto_index> idx(new kma_proto_index);
-  idx->device = device;
-  idx->k = k;
-  idx->n_proto = n_pt;
-  if (n_pt == 0) return *out = idx.release(), KMA_OK;
-  DeviceScope ds(device);
-  if (int rc = ds.entered()) return rc;
-  DevBufs b;
-  AlphabetFlag alpha;
-  uint64_t* d_n;  // [0] pairs, [1] unique keys
-  if (int rc = alpha.init(b)) return rc;
-  KMA_HIP(b.alloc(&d_n, 16));
-  KMA_HIP(hipMemset(d_n, 0, 16));
-  KmerSets p;
-  if (int rc = kmer_sets(b, pres, poff, n_pt, k, alpha.d, p)) return rc;
-  if (int rc = alpha.check()) return rc;
-  const uint64_t pw = std::max<uint64_t>(p.total, 1);
-  uint64_t *pk, *skey, *ukeys;
-  uint32_t *pp, *sproto, *uidx, *ustart;
-  uint8_t* uhead;
-  for (uint64_t** q : {&pk, &skey, &ukeys}) KMA_HIP(b.alloc(q, pw * 8));
-  for (uint32_t** q : {&pp, &sproto, &uidx}) KMA_HIP(b.alloc(q, pw * 4));
-  KMA_HIP(b.alloc(&ustart, (pw + 1) * 4));
-  KMA_HIP(b.alloc(&uhead, pw));
-  Scratch t;
-  KMA_HIP(kma::prim_select_flagged_u64(nullptr, t.ask(), p.sorted, p.first, pk, d_n, p.total, nullptr));
-  KMA_HIP(kma::prim_select_flagged_u32(nullptr, t.ask(), p.owner, p.first, pp, d_n, p.total, nullptr));
-  KMA_HIP(kma::prim_sort_pairs_u64_u32(nullptr, t.ask(), pk, skey, pp, sproto, p.total, 5 * k, nullptr));
-  KMA_HIP(t.alloc(b));
-  KMA_HIP(kma::prim_select_flagged_u64(t.p, t.bytes(), p.sorted, p.first, pk, d_n, p.total, nullptr));
-  KMA_HIP(kma::prim_select_flagged_u32(t.p, t.bytes(), p.owner, p.first, pp, d_n, p.total, nullptr));
-  uint64_t n_pairs = 0, n_u = 0;
-  KMA_HIP(hipMemcpy(&n_pairs, d_n, 8, hipMemcpyDeviceToHost));
-  KMA_HIP(kma::prim_sort_pairs_u64_u32(t.p, t.bytes(), pk, skey, pp, sproto, n_pairs, 5 * k, nullptr));
-  KMA_HIP(kma::launch_run_heads(skey, n_pairs, uhead, uidx, nullptr));
-  KMA_HIP(kma::prim_select_flagged_u64(t.p, t.bytes(), skey, uhead, ukeys, d_n + 1, n_pairs, nullptr));
-  KMA_HIP(kma::prim_select_flagged_u32(t.p, t.bytes(), uidx, uhead, ustart, d_n + 1, n_pairs, nullptr));
-  KMA_HIP(kma::launch_set_end(ustart, d_n + 1, n_pairs, nullptr));
-  KMA_HIP(hipMemcpy(&n_u, d_n + 1, 8, hipMemcpyDeviceToHost));
-  // what stays: exact-size copies (idx frees them on any early return)
-  idx->n_keys = n_u;
-  idx->n_postings = n_pairs;
-  KMA_HIP(hipMalloc(&idx->d_keys, std::max<uint64_t>(n_u, 1) * 8));
-  KMA_HIP(hipMalloc(&idx->d_start, (n_u + 1) * 4));
-  KMA_HIP(hipMalloc(&idx->d_postings, std::max<uint64_t>(n_pairs, 1) * 4));
-  KMA_HIP(hipMalloc(&idx->d_psize, n_pt * 4ull));
-  KMA_HIP(hipMemcpy(idx->d_keys, ukeys, n_u * 8, hipMemcpyDeviceToDevice));
-  KMA_HIP(hipMemcpy(idx->d_start, ustart, (n_u + 1) * 4, hipMemcpyDeviceToDevice));
-  KMA_HIP(hipMemcpy(idx->d_postings, sproto, n_pairs * 4, hipMemcpyDeviceToDevice));
-  KMA_HIP(hipMemcpy(idx->d_psize, p.size, n_pt * 4ull, hipMemcpyDeviceToDevice));
-  KMA_HIP(hipDeviceSynchronize());
-  idx->bytes = n_u * 8 + (n_u + 1) * 4 + n_pairs * 4 + n_pt * 4ull;
-  *out = idx.release();
-  return KMA_OK;
-}
-
-int kma_proto_index_info(const kma_proto_index* idx, struct kma_proto_index_info* out) {
-  if (!idx || !out) return fail(KMA_E_INVALID, "null argument");
-  out->n_proto = idx->n_proto;
-  out->k = idx->k;
-  out->n_keys = idx->n_keys;
-  out->n_postings = idx->n_postings;
-  out->bytes = idx->bytes;
-  return KMA_OK;
-}
-
-int kma_proto_index_destroy(kma_proto_index* idx) {
-  delete idx;
-  return KMA_OK;
-}
-
-int kma_hash_annotate_indexed(const kma_proto_index* idx, const uint8_t* gres,
-                              const uint64_t* goff, uint32_t n_gp, double min_sim,
-                              int32_t* out_best, double* out_sim, uint32_t* out_count,
-                              uint64_t* out_stats) {
-  if (!idx) return fail(KMA_E_INVALID, "null index");
-  if (!(min_sim >= 0.0 && min_sim < 1.0))
-    return fail(KMA_E_INVALID, "Minimum similarity score must be between 0 and 1.");
-  const uint32_t n_pt = idx->n_proto;
-  if ((n_gp && (!out_best || !out_sim)) || (n_pt && !out_count))
-    return fail(KMA_E_INVALID, "null output");
-  if (int rc = check_side(gres, goff, n_gp, "genome protein")) return rc;
-  for (uint32_t i = 0; i < n_gp; ++i) {
-    out_best[i] = -1;
-    out_sim[i] = 0.0;
-  }
-  if (n_pt) std::memset(out_count, 0, n_pt * 4ull);
-  if (out_stats) out_stats[0] = out_stats[1] = out_stats[2] = 0;
-  if (n_gp == 0 || n_pt == 0) return KMA_OK;
-  DeviceScope ds(idx->device);
-  if (int rc = ds.entered()) return rc;
-  DevBufs b;  // the call's scratch: nothing of the index is written
-  AlphabetFlag alpha;
-  if (int rc = alpha.init(b)) return rc;
-  KmerSets g;
-  if (int rc = kmer_sets(b, gres, goff, n_gp, idx->k, alpha.d, g)) return rc;
-  if (int rc = alpha.check()) return rc;
-  kma::HashIndexArgs a{};
-  a.ukeys = idx->d_keys;
-  a.pstart = idx->d_start;
-  a.postings = idx->d_postings;
-  a.psize = idx->d_psize;
-  a.n_u = idx->n_keys;
-  a.n_proto = n_pt;
-  a.gsorted = g.sorted;
-  a.gfirst = g.first;
-  a.goff = g.off;
-  a.gsize = g.size;
-  a.n_gpos = g.total;
-  a.n_genome = n_gp;
-  a.min_sim = min_sim;
-  const int64_t cap = opt(KMA_OPT_HASH_CAP);
-  a.cap = cap > 0 ? (uint32_t)cap : kma::kHashCapDefault;
-  KMA_HIP(b.alloc(&a.gmatch, std::max<uint64_t>(g.total, 1) * 4));
-  KMA_HIP(b.alloc(&a.out_count, n_pt * 4ull));
-  KMA_HIP(b.alloc(&a.out_best, n_gp * 4ull));
-  KMA_HIP(b.alloc(&a.out_sim, n_gp * 8ull));
-  KMA_HIP(b.alloc(&a.stats, 24));
-  KMA_HIP(hipMemset(a.out_count, 0, n_pt * 4ull));
-  KMA_HIP(hipMemset(a.stats, 0, 24));
-  KMA_HIP(kma::launch_index_lookup(a, nullptr));
-  KMA_HIP(kma::launch_index_score(a, nullptr));
-  KMA_HIP(hipMemcpy(out_best, a.out_best, n_gp * 4ull, hipMemcpyDeviceToHost));
-  KMA_HIP(hipMemcpy(out_sim, a.out_sim, n_gp * 8ull, hipMemcpyDeviceToHost));
-  KMA_HIP(hipMemcpy(out_count, a.out_count, n_pt * 4ull, hipMemcpyDeviceToHost));
-  if (out_stats) KMA_HIP(hipMemcpy(out_stats, a.stats, 24, hipMemcpyDeviceToHost));
-  return KMA_OK;
-}
 
 }  // extern "C"
 

@@ -1,5 +1,6 @@
-// kma_hashanno.h — launchers of the hash annotator's scoring kernels (kma_hashanno.hip), used by
-// kma_abi_ops.cpp. Not part of the public ABI (see include/kmeranno.h).
+// kma_hashanno.h — launchers of the hash annotator's candidate and scoring kernels
+// (kma_hashanno.hip), used by kma_abi_sets.cpp; the sets and the genome's postings they score are
+// built by kma_kmersets.hip. Not part of the public ABI (see include/kmeranno.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,11 +38,6 @@ struct HashArgs {
   uint32_t* best_proto;       // per protein: smallest prototype of the slice at that similarity
 };
 
-hipError_t launch_owner_first(const uint64_t* sorted, const uint64_t* off, uint32_t n,
-                              uint32_t* owner, uint8_t* first, hipStream_t s);
-hipError_t launch_run_heads(const uint64_t* k, uint64_t n, uint8_t* head, uint32_t* idx,
-                            hipStream_t s);
-hipError_t launch_set_end(uint32_t* ustart, const uint64_t* n_u, uint64_t n_pairs, hipStream_t s);
 hipError_t launch_cand_count(const HashArgs& a, hipStream_t s);
 hipError_t launch_cand_emit(const HashArgs& a, hipStream_t s);
 hipError_t launch_score(const HashArgs& a, uint64_t n_max, hipStream_t s);
@@ -53,13 +49,6 @@ hipError_t launch_proto_cum(const uint64_t* coff, const uint32_t* ccount, const 
 hipError_t launch_merge_best(uint64_t* best_bits, uint32_t* best_proto, uint64_t* slice_bits,
                              uint32_t* slice_proto, uint32_t n, hipStream_t s);
 hipError_t launch_choose(const HashArgs& a, uint64_t n_max, hipStream_t s);
-hipError_t prim_select_flagged_u64(void* temp, size_t* tb, const uint64_t* in, const uint8_t* f,
-                                  uint64_t* out, uint64_t* n_out, uint64_t n, hipStream_t s);
-hipError_t prim_select_flagged_u32(void* temp, size_t* tb, const uint32_t* in, const uint8_t* f,
-                                  uint32_t* out, uint64_t* n_out, uint64_t n, hipStream_t s);
-hipError_t prim_sort_pairs_u64_u32(void* temp, size_t* tb, const uint64_t* ki, uint64_t* ko,
-                                  const uint32_t* vi, uint32_t* vo, uint64_t n, int bits,
-                                  hipStream_t s);
 hipError_t prim_sort_keys_u64(void* temp, size_t* tb, const uint64_t* ki, uint64_t* ko, uint64_t n,
                              int bits, hipStream_t s);
 hipError_t prim_excl_sum_u32_u64(void* temp, size_t* tb, const uint32_t* in, uint64_t* out,

@@ -10,9 +10,9 @@
 // is >= minSim and above the current one (earlier prototypes win ties).
 //
 // GPU form (sorts and scans; no per-pair loop):
-//   genome:     window keys, per-protein segmented sort, distinct sizes, (key, protein) pairs
+//   genome:     its ProteinKmers sets and their postings (kma_kmersets.hip): (key, protein) pairs
 //               of distinct keys sorted by key, unique keys U with their protein ranges
-//   prototypes: window keys, segmented sort, distinct sizes; every distinct key looked up in U
+//   prototypes: their ProteinKmers sets (kma_kmersets.hip); every distinct key looked up in U
 //               (binary search) and one candidate (prototype, protein) emitted per protein of
 //               its range; candidates sorted and run-length encoded: the run length IS the
 //               number of shared distinct kmers
@@ -23,61 +23,15 @@
 #include <rocprim/rocprim.hpp>
 
 #include "kma_hashanno.h"
+#include "kma_kmersets.h"
 
 namespace kma {
 namespace {
 
-constexpr uint64_t kSent = ~0ull;
-
-unsigned grid1(uint64_t n) {
-  const uint64_t g = (n + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
-unsigned grid_w(uint64_t n) {  // wave per item
-  const uint64_t g = (n + 3) / 4;
-  return (unsigned)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
-}
-
-// Wave per protein: owner[p] = protein of position p; first[p] = 1 at the first occurrence of a
-// non-sentinel key in the protein's sorted segment.
-__global__ __launch_bounds__(256) void owner_first_kernel(const uint64_t* __restrict__ sorted,
-                                                          const uint64_t* __restrict__ off,
-                                                          uint32_t n, uint32_t* __restrict__ owner,
-                                                          uint8_t* __restrict__ first) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t o0 = off[0];
-  for (uint64_t s = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); s < n;
-       s += (uint64_t)gridDim.x * 4) {
-    const uint64_t lo = off[s] - o0, hi = off[s + 1] - o0;
-    for (uint64_t p = lo + lane; p < hi; p += 64) {
-      const uint64_t v = sorted[p];
-      owner[p] = (uint32_t)s;
-      first[p] = (v != kSent && (p == lo || sorted[p - 1] != v)) ? 1 : 0;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void run_heads_kernel(const uint64_t* __restrict__ k,
-                                                        uint64_t n, uint8_t* __restrict__ head,
-                                                        uint32_t* __restrict__ idx) {
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) {
-    head[i] = (i == 0 || k[i] != k[i - 1]) ? 1 : 0;
-    idx[i] = (uint32_t)i;
-  }
-}
-
-__global__ void set_end_kernel(uint32_t* ustart, const uint64_t* n_u, uint64_t n_pairs) {
-  ustart[*n_u] = (uint32_t)n_pairs;
-}
-
-// Largest u with U[u] <= v, or n if none / not equal.
+// The u with U[u] == v, or n if there is none.
 __device__ __forceinline__ uint64_t find_key(const uint64_t* __restrict__ U, uint64_t n,
                                              uint64_t v) {
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (U[mid] < v) lo = mid + 1; else hi = mid;
-  }
+  const uint64_t lo = lower_bound(U, 0, n, v);
   return (lo < n && U[lo] == v) ? lo : n;
 }
 
@@ -185,21 +139,6 @@ hipError_t launch_merge_best(uint64_t* best_bits, uint32_t* best_proto, uint64_t
   return hipGetLastError();
 }
 
-hipError_t launch_owner_first(const uint64_t* sorted, const uint64_t* off, uint32_t n,
-                              uint32_t* owner, uint8_t* first, hipStream_t s) {
-  hipLaunchKernelGGL(owner_first_kernel, dim3(grid_w(n)), dim3(256), 0, s, sorted, off, n, owner,
-                     first);
-  return hipGetLastError();
-}
-hipError_t launch_run_heads(const uint64_t* k, uint64_t n, uint8_t* head, uint32_t* idx,
-                            hipStream_t s) {
-  hipLaunchKernelGGL(run_heads_kernel, dim3(grid1(n)), dim3(256), 0, s, k, n, head, idx);
-  return hipGetLastError();
-}
-hipError_t launch_set_end(uint32_t* ustart, const uint64_t* n_u, uint64_t n_pairs, hipStream_t s) {
-  hipLaunchKernelGGL(set_end_kernel, dim3(1), dim3(1), 0, s, ustart, n_u, n_pairs);
-  return hipGetLastError();
-}
 hipError_t launch_cand_count(const HashArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(cand_count_kernel, dim3(grid1(a.n_ppos)), dim3(256), 0, s, a);
   return hipGetLastError();
@@ -218,19 +157,6 @@ hipError_t launch_choose(const HashArgs& a, uint64_t n_max, hipStream_t s) {
 }
 
 // rocPRIM wrappers (temp == nullptr: size query).
-hipError_t prim_select_flagged_u64(void* temp, size_t* tb, const uint64_t* in, const uint8_t* f,
-                                  uint64_t* out, uint64_t* n_out, uint64_t n, hipStream_t s) {
-  return rocprim::select(temp, *tb, in, f, out, n_out, (size_t)n, s);
-}
-hipError_t prim_select_flagged_u32(void* temp, size_t* tb, const uint32_t* in, const uint8_t* f,
-                                  uint32_t* out, uint64_t* n_out, uint64_t n, hipStream_t s) {
-  return rocprim::select(temp, *tb, in, f, out, n_out, (size_t)n, s);
-}
-hipError_t prim_sort_pairs_u64_u32(void* temp, size_t* tb, const uint64_t* ki, uint64_t* ko,
-                                  const uint32_t* vi, uint32_t* vo, uint64_t n, int bits,
-                                  hipStream_t s) {
-  return rocprim::radix_sort_pairs(temp, *tb, ki, ko, vi, vo, (size_t)n, 0u, (unsigned)bits, s);
-}
 hipError_t prim_sort_keys_u64(void* temp, size_t* tb, const uint64_t* ki, uint64_t* ko, uint64_t n,
                              int bits, hipStream_t s) {
   return rocprim::radix_sort_keys(temp, *tb, ki, ko, (size_t)n, 0u, (unsigned)bits, s);

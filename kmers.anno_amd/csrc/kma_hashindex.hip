@@ -23,6 +23,7 @@
 // prototype lies in exactly one scored range and all arithmetic is integer counts and one double
 // division, so the results do not depend on CAP or on scheduling.
 #include "kma_hashindex.h"
+#include "kma_kmersets.h"
 
 namespace kma {
 namespace {
@@ -36,11 +37,7 @@ __global__ __launch_bounds__(256) void index_lookup_kernel(HashIndexArgs a) {
     uint32_t m = kHashEmpty;
     if (a.gfirst[i]) {
       const uint64_t v = a.gsorted[i];
-      uint64_t lo = 0, hi = a.n_u;
-      while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a.ukeys[mid] < v) lo = mid + 1; else hi = mid;
-      }
+      const uint64_t lo = lower_bound(a.ukeys, 0, a.n_u, v);
       if (lo < a.n_u && a.ukeys[lo] == v) m = (uint32_t)lo;
     }
     a.gmatch[i] = m;
@@ -213,9 +210,7 @@ __global__ __launch_bounds__(256) void index_score_kernel(HashIndexArgs a, uint3
 }  // namespace
 
 hipError_t launch_index_lookup(const HashIndexArgs& a, hipStream_t s) {
-  const uint64_t g = (a.n_gpos + 255) / 256;
-  hipLaunchKernelGGL(index_lookup_kernel, dim3((unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g))),
-                     dim3(256), 0, s, a);
+  hipLaunchKernelGGL(index_lookup_kernel, dim3(grid1(a.n_gpos)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -1,8 +1,8 @@
 // kma_host.h — host-side plumbing shared by the units of the C ABI (kma_host.cpp, kma_abi_*.cpp):
 // the error string, HIP call checking, device scopes and buffers, the option store, the staging
-// pool, and the batch-setup helpers of the one-shot operators (kma_abi_ops.cpp). Private to the
-// library, not installed. Per-process state (the options, the staging pool, the thread's error
-// string and shard width) is defined once, in kma_host.cpp.
+// pool, and the batch-setup helpers of the one-shot operators (kma_abi_ops.cpp,
+// kma_abi_sets.cpp). Private to the library, not installed. Per-process state (the options, the
+// staging pool, the thread's error string and shard width) is defined once, in kma_host.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -264,7 +264,7 @@ int fan_out(int n, F f) {
   return KMA_OK;
 }
 
-// ---- batch setup of the one-shot operators (kma_abi_ops.cpp) ------------------------------------
+// ---- batch setup of the one-shot operators (kma_abi_ops.cpp, kma_abi_sets.cpp) ------------------
 // The n + 1 offsets of a batch (n == 0: not read): KMA_E_INVALID "[<what> ]offsets decrease at
 // <s>" at the first s with offsets[s + 1] < offsets[s] (what may be ""); then, with the message
 // `too_long`, when offsets[n] - offsets[0] reaches limit (0: no limit).

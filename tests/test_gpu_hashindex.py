@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle_py
+from test_gpu_set_ops import BASE, batch_shapes, hash_shared_case, mutate, pack, shared_input
 
 pytestmark = pytest.mark.gpu
 AA = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY", np.uint8)
@@ -222,6 +223,40 @@ def test_indexed_edges(kma, oracle_c):
         got = shape.indexed(cap=cap)
         assert (got[0] == best).all() and (got[1] == sim).all() and (got[2] == cnt).all()
         assert int(got[3][1]) == (1 if cap == 16 else 2)  # the long one; at CAP 1 also the copy
+
+
+@pytest.mark.parametrize("k", [2, 8, 12])
+def test_indexed_views_and_edge_batches(kma, oracle_c, k):
+    """Both sides as views into larger buffers (offsets[0] = 37, other residues around them), on
+    test_gpu_set_ops.py's shared proteins (a few dozen short ones) and its batch shapes on either
+    side: an empty protein first, last and two adjacent, a side of only empty proteins, a side in
+    which no protein reaches K. The index built from a view and queried with a view gives the
+    oracle's and kma_hash_annotate's results on the same views, and those of the base-0 run."""
+    genome, protos = hash_shared_case(k)
+    small_g = [genome[i] for i in shared_input(k).small]
+    small_p = [p for p in protos if len(p) < 1000]
+    assert 30 <= len(small_g) <= 60 and 30 <= len(small_p) <= 60
+    sides = [(small_g, small_p)]
+    for batch in batch_shapes(k):
+        sides += [(batch, [mutate(p, 3 * k, 1) for p in batch] + batch[:1]), (batch, small_p),
+                  (small_g, batch)]
+    annotated = 0
+    for g, p in sides:
+        runs = []
+        for base in (BASE, 0):
+            (gr, go), (pr, po) = pack(g, base), pack(p, base)
+            assert int(go[0]) == int(po[0]) == base
+            with kma.ProtoIndex(pr, po, k=k) as idx:
+                got = kma.hash_annotate_indexed(idx, gr, go, 0.0125)
+            for other in (oracle_c.hash_annotate(gr, go, pr, po, k, 0.0125),
+                          kma.hash_annotate(gr, go, pr, po, k, 0.0125)):
+                for a, b in zip(got, other):
+                    assert (a == b).all(), (len(g), len(p), base)
+            runs.append(got)
+        for a, b in zip(*runs):
+            assert (a == b).all(), (len(g), len(p))
+        annotated += int((runs[0][0] >= 0).sum())
+    assert annotated > 60  # (the shapes are not all empty: most short proteins find their copy)
 
 
 def test_indexed_rejects_lowercase_on_either_side(kma):

@@ -15,8 +15,8 @@ from test_gpu_set_ops import (HASH_SCALE_CASES, BEST_EDGE_CASES, BEST_EDGE_PROTS
                               long_run_case, pack, proposal_edge_case, proposal_scale_case,
                               random_conns, shared_input, shared_lengths, shared_pairs)
 
-GRID1_CAP = 8192 * 256       # kma_hashanno.hip grid1: items per trip
-WAVE_CAP = 16384 * 4         # grid_waves / grid_w: proteins or pairs per trip
+GRID1_CAP = 8192 * 256       # kma_kmersets.h grid1: items per trip
+WAVE_CAP = 16384 * 4         # kma_kmersets.h grid_waves: proteins or pairs per trip
 BUILD_CAP = 8192 * 4         # launch_build_windows: proteins per trip
 PROPOSAL_CAP = 4096 * 256    # kma_proposals.hip grid_of: connections per trip
 
