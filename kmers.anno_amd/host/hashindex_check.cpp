@@ -5,6 +5,11 @@
 // writes the case files and runs it).
 //
 //   kma_hashindex_check CASE
+//   kma_hashindex_check --hash CAP [ID ...]
+//
+// --hash prints "slots T bits B" of hash_table_slots(CAP) and then one line "ID SLOT" of
+// hash_slot(ID, B) per prototype id: tests/test_hashindex_workload.py holds its Python mirror of
+// the two functions to these.
 //
 // CASE: u32 n_proto, u32 n_genome, u32 cap, u32 0, f64 min_sim; then per prototype and then per
 // genome protein a u32 count and that many u64 window keys (any order, repeats allowed: the
@@ -17,7 +22,9 @@
 // the posting lengths, the flattened postings into the open-addressed table, the overflow split
 // on the range stack, the sweep with the running best. Every protein's best, similarity bits,
 // shared count, candidate count and split flag, and every prototype's match count, must equal a
-// brute-force count over all pairs, and the file's expectations.
+// brute-force count over all pairs, and the file's expectations. The "ok" line ends with the
+// longest probe of any insert (slots looked at) and whether a probe passed from the table's last
+// slot to slot 0.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -113,6 +120,11 @@ void build_index(const Case& c, Index* ix) {
   ix->pstart[ix->n_u] = (uint32_t)pairs.size();
 }
 
+struct Probes {
+  uint32_t longest = 0;  // slots looked at by one table_add
+  bool wrapped = false;  // a probe went on from slot T - 1 to slot 0
+};
+
 struct Result {
   uint32_t best = kHashEmpty, shared = 0, cand = 0, ranges = 0;
   uint64_t bits = 0;
@@ -121,10 +133,12 @@ struct Result {
 
 // table_add of kma_hashindex.hip without its atomics.
 void table_add(uint32_t* ids, uint32_t* cnt, uint32_t* distinct, uint32_t proto, uint32_t bits,
-               uint32_t cap) {
+               uint32_t cap, Probes* pr) {
   const uint32_t mask = (1u << bits) - 1u;
   uint32_t h = kma::hash_slot(proto, bits);
   for (uint32_t probe = 0; probe <= mask; ++probe, h = (h + 1) & mask) {
+    pr->longest = std::max(pr->longest, probe + 1);
+    if (probe && h == 0) pr->wrapped = true;
     if (ids[h] == kHashEmpty) {
       if (*distinct > cap) return;
       ids[h] = proto;
@@ -141,7 +155,7 @@ void table_add(uint32_t* ids, uint32_t* cnt, uint32_t* distinct, uint32_t proto,
 
 // One block: genome protein `keys` (sorted, repeats kept) against the index.
 Result run_block(const Case& c, const Index& ix, const std::vector<uint64_t>& keys,
-                 std::vector<uint32_t>* out_count) {
+                 std::vector<uint32_t>* out_count, Probes* pr) {
   Result r;
   const uint32_t gsize = distinct_size(keys);
   std::vector<uint32_t> gmatch(keys.size(), kHashEmpty);  // index_lookup_kernel
@@ -184,7 +198,8 @@ Result run_block(const Case& c, const Index& ix, const std::vector<uint64_t>& ke
       pre[kHashBlock] = total;
       for (uint32_t j = 0; j < total; ++j) {
         const uint32_t key = kma::prefix_owner(pre, kHashBlock, j);
-        table_add(ids, cnt, &distinct, ix.postings[start[key] + (j - pre[key])], bits, c.cap);
+        table_add(ids, cnt, &distinct, ix.postings[start[key] + (j - pre[key])], bits, c.cap,
+                  pr);
       }
     }
     if (first) r.cand = distinct;  // (of [0, n_proto): exact only when it did not overflow)
@@ -234,10 +249,26 @@ int wrong(uint32_t g, const char* what, long long got, long long want) {
   return 1;
 }
 
+// --hash CAP [ID ...]: the table of a CAP and the first slots of prototype ids in it.
+int print_hash(int argc, char** argv) {
+  const unsigned long cap = std::strtoul(argv[2], nullptr, 10);
+  if (cap < 1 || cap > kma::kHashCapMax)
+    return std::fprintf(stderr, "hashindex_check: CAP is 1..%u\n", kma::kHashCapMax), 2;
+  const uint32_t slots = kma::hash_table_slots((uint32_t)cap), bits = kma::hash_log2(slots);
+  std::printf("slots %u bits %u\n", slots, bits);
+  for (int i = 3; i < argc; ++i) {
+    const uint32_t id = (uint32_t)std::strtoul(argv[i], nullptr, 10);
+    std::printf("%u %u\n", id, kma::hash_slot(id, bits));
+  }
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc != 2) return std::fprintf(stderr, "usage: kma_hashindex_check CASE\n"), 2;
+  if (argc >= 3 && !std::strcmp(argv[1], "--hash")) return print_hash(argc, argv);
+  if (argc != 2)
+    return std::fprintf(stderr, "usage: kma_hashindex_check CASE | --hash CAP [ID ...]\n"), 2;
   Case c;
   if (!read_case(argv[1], &c) || c.cap < 1 || c.cap > kma::kHashCapMax)
     return std::fprintf(stderr, "hashindex_check: cannot read %s\n", argv[1]), 2;
@@ -245,8 +276,9 @@ int main(int argc, char** argv) {
   build_index(c, &ix);
   std::vector<uint32_t> count(c.n_proto, 0), brute_count(c.n_proto, 0);
   uint32_t n_split = 0, n_ranges = 0;
+  Probes probes;
   for (uint32_t g = 0; g < c.n_genome; ++g) {
-    const Result r = run_block(c, ix, c.genome[g], &count);
+    const Result r = run_block(c, ix, c.genome[g], &count, &probes);
     // all pairs, in file order: a proposal needs sim >= min_sim and above the current one
     const uint32_t gsize = distinct_size(c.genome[g]);
     int32_t best = -1;
@@ -277,7 +309,8 @@ int main(int argc, char** argv) {
   }
   for (uint32_t p = 0; p < c.n_proto; ++p)
     if (count[p] != brute_count[p]) return wrong(p, "prototype match count", count[p], brute_count[p]);
-  std::printf("hashindex_check ok: %u prototypes, %u proteins, %u split, %u ranges\n", c.n_proto,
-              c.n_genome, n_split, n_ranges);
+  std::printf("hashindex_check ok: %u prototypes, %u proteins, %u split, %u ranges, "
+              "longest probe %u, wrapped %u\n",
+              c.n_proto, c.n_genome, n_split, n_ranges, probes.longest, probes.wrapped ? 1u : 0u);
   return 0;
 }
