@@ -214,6 +214,10 @@ int kma_device_count(int* out_n);
  *   KMA_OPT_HOST_PIECE_MIN  host protein calls: fewest residues per pipeline piece [0: 2^24]; a
  *                           call runs min(KMA_OPT_HOST_PIECES, residues / this) pieces (ABI 7;
  *                           tests set it low to run many pieces on small batches)
+ *   KMA_OPT_HASH_LDS_KEYS   kma_hash_annotate_indexed_device: window keys a genome protein's
+ *                           workgroup sorts in LDS at a time [0: 4096]; a protein of more windows
+ *                           is sorted in runs of this many (results do not depend on it); a power
+ *                           of two in 64..4096 (tests set it low)
  * kma_workspace_option_set overrides KMA_OPT_BLOCK_PROTEINS / KMA_OPT_DEFER for the _device
  * calls made with one workspace (KMA_OPT_DEFAULT: follow the library default again).        */
 #define KMA_OPT_LAYOUT 1
@@ -227,6 +231,7 @@ int kma_device_count(int* out_n);
 #define KMA_OPT_PLACEMENT 9
 #define KMA_OPT_HOST_PIECE_MIN 10
 #define KMA_OPT_HASH_CAP 12
+#define KMA_OPT_HASH_LDS_KEYS 13
 #define KMA_OPT_DEFAULT INT64_MIN
 int kma_option_set(int option, int64_t value);
 int kma_option_get(int option, int64_t* value);
@@ -618,6 +623,35 @@ int kma_hash_annotate_indexed(const kma_proto_index* index, const uint8_t* genom
                               const uint64_t* genome_offsets, uint32_t n_genome, double min_sim,
                               int32_t* out_best, double* out_sim, uint32_t* out_count,
                               uint64_t* out_stats);
+
+/* ---- the indexed call on a device-resident batch (added under ABI 7) -------------------------
+ * kma_hash_annotate_indexed_device scores a genome whose proteins already lie on the index's
+ * device, in the layout of kma_annotate_proteins_device and kma_sequence_md5_device: every d_*
+ * pointer is device memory there; the d_residues base is 8-byte aligned and readable for 32
+ * bytes past d_offsets[n_genome]; d_offsets[0] need not be 0 and nothing before the aligned word
+ * of residue d_offsets[0] is read; n_residues = d_offsets[n_genome] - d_offsets[0], below 2^31.
+ * The semantics are kma_hash_annotate_indexed's exactly (same sets, same double similarity,
+ * earlier prototypes win ties, d_count per call, d_stats[0..2] = out_stats). d_stats (required)
+ * has 4 words: d_stats[3] is nonzero iff a window of the batch holds a byte outside A-Z / '*'
+ * (it stands for KMA_E_ALPHABET, which an asynchronous call cannot return; the other outputs are
+ * then unspecified); a byte outside the alphabet that lies in no window does not set it.
+ * The call is asynchronous on `stream`: no allocation, no host synchronisation, no copy to the
+ * host, no state left behind. What it enqueues is one chain of kernels on that stream (one that
+ * zeroes d_count and d_stats, genome_sets_kernel, index_score_kernel: kma_hashsets.hip,
+ * kma_hashindex.hip), so it can be captured in a graph. n_genome == 0 enqueues nothing; for an index of no prototypes
+ * the stream sets every d_best to -1, every d_sim to 0.0 and d_stats to zero (d_count may then
+ * be null). d_scratch: 16-byte aligned, at least kma_hash_scratch_bytes(n_residues, n_genome)
+ * bytes (a pure host function, monotone in both arguments); the call reads none of it that it
+ * has not written. KMA_OPT_HASH_CAP applies as to the host entry.
+ * KMA_E_INVALID before any device is touched: a null index or pointer, d_residues not 8-byte or
+ * d_scratch not 16-byte aligned, scratch_bytes too small, n_residues >= 2^31, min_sim outside
+ * [0, 1).                                                                                     */
+uint64_t kma_hash_scratch_bytes(uint64_t n_residues, uint32_t n_genome);
+int kma_hash_annotate_indexed_device(const kma_proto_index* index, const uint8_t* d_residues,
+                                     const uint64_t* d_offsets, uint32_t n_genome,
+                                     uint64_t n_residues, double min_sim, void* d_scratch,
+                                     uint64_t scratch_bytes, int32_t* d_best, double* d_sim,
+                                     uint32_t* d_count, uint64_t* d_stats, void* stream);
 
 /* ---- signature-table construction (BuildKmerProcessor.java:137-223, RoleCounter.java) -------
  * After role resolution by the host (Feature.getUsefulRoles + the interesting-role filter):

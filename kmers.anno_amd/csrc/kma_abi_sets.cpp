@@ -6,12 +6,15 @@
 // and range starts. Each entry checks its arguments on the host, enters its device, stages its
 // batch in buffers of its own (kma_host.h), runs its launchers (kma_kmersets.hip,
 // kma_distance.hip, kma_hashanno.hip, kma_hashindex.hip) on the null stream and copies the
-// results back.
+// results back. kma_hash_annotate_indexed_device is the exception: its batch is on the device
+// already, it stages and copies nothing, and it enqueues its two kernels (kma_hashsets.hip,
+// kma_hashindex.hip) on the caller's stream.
 #include <memory>
 
 #include "kma_distance.h"
 #include "kma_hashanno.h"
 #include "kma_hashindex.h"
+#include "kma_hashsets.h"
 #include "kma_internal.h"
 #include "kma_kmersets.h"
 #include "kma_objects.h"
@@ -470,6 +473,81 @@ int kma_hash_annotate_indexed(const kma_proto_index* idx, const uint8_t* gres,
   KMA_HIP(hipMemcpy(out_sim, a.out_sim, n_gp * 8ull, hipMemcpyDeviceToHost));
   KMA_HIP(hipMemcpy(out_count, a.out_count, n_pt * 4ull, hipMemcpyDeviceToHost));
   if (out_stats) KMA_HIP(hipMemcpy(out_stats, a.stats, 24, hipMemcpyDeviceToHost));
+  return KMA_OK;
+}
+
+// ---- the indexed call on a device-resident batch (kma_hashsets.hip) ----------------------------
+uint64_t kma_hash_scratch_bytes(uint64_t n_residues, uint32_t n_genome) {
+  return kma::hash_scratch_layout(n_residues, n_genome).bytes;
+}
+
+// One chain on `stream`: hash_reset_kernel (d_count and d_stats to zero), genome_sets_kernel
+// (gmatch and gsize of the batch into the scratch), index_score_kernel (unchanged: it reads gmatch over the
+// proteins' segments, gsize and the offsets, and writes the outputs itself).
+int kma_hash_annotate_indexed_device(const kma_proto_index* idx, const uint8_t* d_residues,
+                                     const uint64_t* d_offsets, uint32_t n_gp,
+                                     uint64_t n_residues, double min_sim, void* d_scratch,
+                                     uint64_t scratch_bytes, int32_t* d_best, double* d_sim,
+                                     uint32_t* d_count, uint64_t* d_stats, void* stream) {
+  if (!idx) return fail(KMA_E_INVALID, "null index");
+  if (!(min_sim >= 0.0 && min_sim < 1.0))
+    return fail(KMA_E_INVALID, "Minimum similarity score must be between 0 and 1.");
+  if (n_residues >= (1ull << 31))
+    return fail(KMA_E_INVALID, "more than 2^31 genome protein residues");
+  if (n_gp == 0) return KMA_OK;
+  const uint32_t n_pt = idx->n_proto;
+  if (!d_residues || !d_offsets || !d_scratch) return fail(KMA_E_INVALID, "null argument");
+  if (!d_best || !d_sim || !d_stats || (n_pt && !d_count))
+    return fail(KMA_E_INVALID, "null output");
+  if (reinterpret_cast<uintptr_t>(d_residues) & 7u)
+    return fail(KMA_E_INVALID, "d_residues is not 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_scratch) & 15u)
+    return fail(KMA_E_INVALID, "d_scratch is not 16-byte aligned");
+  const kma::HashScratchLayout lay = kma::hash_scratch_layout(n_residues, n_gp);
+  if (scratch_bytes < lay.bytes)
+    return fail(KMA_E_INVALID, "scratch of %llu bytes, %llu needed",
+                (unsigned long long)scratch_bytes, (unsigned long long)lay.bytes);
+  DeviceScope ds(idx->device);
+  if (int rc = ds.entered()) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned long long* stats = reinterpret_cast<unsigned long long*>(d_stats);
+  KMA_HIP(kma::launch_hash_reset(d_count, n_pt, stats, d_best, d_sim, n_pt ? 0 : n_gp, s));
+  if (n_pt == 0) return KMA_OK;
+  uint8_t* scratch = static_cast<uint8_t*>(d_scratch);
+  kma::GenomeSetsArgs g{};
+  g.res = d_residues;
+  g.off = d_offsets;
+  g.n_genome = n_gp;
+  g.k = idx->k;
+  const int64_t w = opt(KMA_OPT_HASH_LDS_KEYS);
+  g.w = w > 0 ? (uint32_t)w : kma::kSetsKeysMax;
+  g.ukeys = idx->d_keys;
+  g.n_u = idx->n_keys;
+  g.gmatch = reinterpret_cast<uint32_t*>(scratch + lay.gmatch);
+  g.gsize = reinterpret_cast<uint32_t*>(scratch + lay.gsize);
+  g.runs = reinterpret_cast<uint64_t*>(scratch + lay.runs);
+  g.alpha = stats + 3;
+  kma::HashIndexArgs a{};
+  a.ukeys = idx->d_keys;
+  a.pstart = idx->d_start;
+  a.postings = idx->d_postings;
+  a.psize = idx->d_psize;
+  a.n_u = idx->n_keys;
+  a.n_proto = n_pt;
+  a.goff = d_offsets;
+  a.gsize = g.gsize;
+  a.n_gpos = n_residues;
+  a.n_genome = n_gp;
+  a.gmatch = g.gmatch;
+  a.min_sim = min_sim;
+  const int64_t cap = opt(KMA_OPT_HASH_CAP);
+  a.cap = cap > 0 ? (uint32_t)cap : kma::kHashCapDefault;
+  a.out_count = d_count;
+  a.out_best = d_best;
+  a.out_sim = d_sim;
+  a.stats = stats;
+  KMA_HIP(kma::launch_genome_sets(g, s));
+  KMA_HIP(kma::launch_index_score(a, s));
   return KMA_OK;
 }
 

@@ -20,9 +20,9 @@ namespace host {
 // environment is read only by tuning builds (-DKMA_TUNING_ENV=1, the A/B scripts' variants):
 // a library a JVM loads must not change its kernel geometry because of a stray variable.
 namespace {
-constexpr int kNumOpts = 13;  // (number 11 is no option: include/kmeranno.h)
+constexpr int kNumOpts = 14;  // (number 11 is no option: include/kmeranno.h)
 std::atomic<int64_t> g_opt[kNumOpts] = {{0}, {-1}, {0}, {-1}, {0}, {0}, {1}, {0},
-                                         {0}, {-1}, {0}, {0}, {0}};
+                                         {0}, {-1}, {0}, {0}, {0}, {0}};
 }  // namespace
 
 bool option_valid(int opt, int64_t v) {
@@ -38,6 +38,8 @@ bool option_valid(int opt, int64_t v) {
     case KMA_OPT_HOST_PIECE_MIN: return v >= 0 && v <= (int64_t)(1ull << 32);
     case KMA_OPT_PLACEMENT: return v >= -1 && v <= 1;
     case KMA_OPT_HASH_CAP: return v >= 0 && v <= 2048;  // kma_hashindex.h kHashCapMax
+    case KMA_OPT_HASH_LDS_KEYS:  // kma_hashsets.h kSetsKeysMin .. kSetsKeysMax
+      return v == 0 || (v >= 64 && v <= 4096 && (v & (v - 1)) == 0);
     default: return false;
   }
 }

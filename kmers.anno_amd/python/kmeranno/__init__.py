@@ -50,15 +50,17 @@ EXPORTS = (
     "kma_sequence_md5_device", "kma_sequence_md5", "kma_check_sequences",
     "kma_proto_index_create", "kma_proto_index_info", "kma_proto_index_destroy",
     "kma_hash_annotate_indexed",
+    "kma_hash_scratch_bytes", "kma_hash_annotate_indexed_device",
 )
 
 # Tuning options (include/kmeranno.h "options"): library-wide defaults read per call.
 OPT_LAYOUT, OPT_BLOCK_PROTEINS, OPT_DEFER, OPT_HOST_PIECES, OPT_HASH_SLICE = 1, 2, 3, 4, 5
 OPT_PACKED_INPUT, OPT_HOST_THREADS, OPT_HOST_SLICE, OPT_PLACEMENT = 6, 7, 8, 9
-OPT_HOST_PIECE_MIN, OPT_HASH_CAP = 10, 12  # (11 is no option)
+OPT_HOST_PIECE_MIN, OPT_HASH_CAP, OPT_HASH_LDS_KEYS = 10, 12, 13  # (11 is no option)
 OPT_DEFAULTS = {OPT_LAYOUT: -1, OPT_BLOCK_PROTEINS: 0, OPT_DEFER: -1, OPT_HOST_PIECES: 0,
                 OPT_HASH_SLICE: 0, OPT_PACKED_INPUT: 1, OPT_HOST_THREADS: 0, OPT_HOST_SLICE: 0,
-                OPT_PLACEMENT: -1, OPT_HOST_PIECE_MIN: 0, OPT_HASH_CAP: 0}
+                OPT_PLACEMENT: -1, OPT_HOST_PIECE_MIN: 0, OPT_HASH_CAP: 0,
+                OPT_HASH_LDS_KEYS: 0}
 LAYOUT_TWO_CHOICE = 0x100  # layout code flag: two-choice placement (include/kmeranno.h)
 LAYOUT_MOD_SAMPLING = 0x40  # layout code flag: the mod-sampling minimizer order (K = 8, m = 6)
 OPT_DEFAULT = -(1 << 63)  # kma_workspace_option_set: follow the library default
@@ -66,7 +68,8 @@ _OPT_NAMES = {"layout": OPT_LAYOUT, "block_proteins": OPT_BLOCK_PROTEINS, "defer
               "host_pieces": OPT_HOST_PIECES, "hash_slice": OPT_HASH_SLICE,
               "packed_input": OPT_PACKED_INPUT, "host_threads": OPT_HOST_THREADS,
               "host_slice": OPT_HOST_SLICE, "placement": OPT_PLACEMENT,
-              "host_piece_min": OPT_HOST_PIECE_MIN, "hash_cap": OPT_HASH_CAP}
+              "host_piece_min": OPT_HOST_PIECE_MIN, "hash_cap": OPT_HASH_CAP,
+              "hash_lds_keys": OPT_HASH_LDS_KEYS}
 
 
 class KmerAnnoError(RuntimeError):
@@ -192,6 +195,10 @@ def load(path: str | None = None):
         L.kma_proto_index_destroy.argtypes = [_vp]
         L.kma_hash_annotate_indexed.argtypes = [_vp, _vp, _vp, _u32, C.c_double, _vp, _vp, _vp,
                                                 _vp]
+        L.kma_hash_scratch_bytes.restype = _u64
+        L.kma_hash_scratch_bytes.argtypes = [_u64, _u32]
+        L.kma_hash_annotate_indexed_device.argtypes = [_vp, _vp, _vp, _u32, _u64, C.c_double,
+                                                       _vp, _u64, _vp, _vp, _vp, _vp, _vp]
         L.kma_debug_translate_ms.restype = C.c_double
         L.kma_debug_translate_ms.argtypes = []
         L.kma_contig_window_count.restype = _u64
@@ -926,6 +933,27 @@ def hash_annotate_indexed(index: ProtoIndex, genome_residues, genome_offsets,
                                             sim.ctypes.data, cnt.ctypes.data, st.ctypes.data))
     out = (best[:n_g], sim[:n_g], cnt[:n_p])
     return out + (st,) if stats else out
+
+
+def hash_scratch_bytes(n_residues: int, n_genome: int) -> int:
+    """kma_hash_scratch_bytes: the device scratch hash_annotate_indexed_device needs for a batch
+    of n_genome proteins and n_residues residues (a host function, monotone in both)."""
+    return int(load().kma_hash_scratch_bytes(n_residues, n_genome))
+
+
+def hash_annotate_indexed_device(index: ProtoIndex, d_residues: int, d_offsets: int,
+                                 n_genome: int, n_residues: int, d_scratch: int,
+                                 scratch_bytes: int, d_best: int, d_sim: int, d_count: int,
+                                 d_stats: int, min_sim: float = 0.0125, stream: int = 0):
+    """kma_hash_annotate_indexed_device (asynchronous on `stream`: memsets and two kernels, no
+    allocation, no copy): hash_annotate_indexed for a genome already on the index's device, in
+    the layout and padding of annotate_proteins_device. Integer device pointers; d_best int32
+    and d_sim float64 per protein, d_count uint32 per prototype, d_stats 4 uint64 (the host
+    entry's three, then nonzero iff a window holds a byte outside the alphabet)."""
+    _check(load().kma_hash_annotate_indexed_device(
+        index.handle, d_residues or None, d_offsets or None, n_genome, n_residues, min_sim,
+        d_scratch or None, scratch_bytes, d_best or None, d_sim or None, d_count or None,
+        d_stats or None, stream or None))
 
 
 def build_signatures(residues: np.ndarray, offsets: np.ndarray, roles, k: int = 8,
