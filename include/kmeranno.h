@@ -669,6 +669,48 @@ int kma_build_signatures(const uint8_t* residues, const uint64_t* offsets, const
                          uint32_t n_seq, int k, uint32_t flags, int device, uint64_t* out_keys,
                          uint32_t* out_roles, uint64_t cap, uint64_t* n_out);
 
+/* ---- streamed signature build (added under ABI 7) ---------------------------------------------
+ * kma_build_signatures for a training set that is fed batch by batch (genome by genome): the
+ * builder keeps, on its device, one row per distinct kmer seen so far with the kmer's state (its
+ * one role / hit by two different roles / held by a buffered protein), and every add reduces its
+ * batch to such rows (window packing, radix sort, a fold per key run) and merges them into the
+ * resident rows (a merge-path union; equal keys combine their states). The combine is
+ * associative, commutative and idempotent, so kma_sig_builder_finish returns exactly the rows of
+ * kma_build_signatures on the concatenation of the adds, whatever the split into adds and their
+ * order. k (1..12), flags (KMA_F_END_EXCLUSIVE only), roles and the output rows (ascending by
+ * packed key, no duplicates) mean what they mean for kma_build_signatures.
+ * Limits: fewer than 2^31 residues per add; no limit over the builder's life; fewer than 2^32
+ * resident kmers (one more: KMA_E_CAPACITY, the builder as it was).
+ * kma_sig_builder_add is synchronous and all-or-nothing: on KMA_E_ALPHABET (a counted window
+ * holds a byte outside A-Z / '*'), KMA_E_INVALID (decreasing offsets, a role >= 2^24 - 1, 2^31
+ * residues or more), KMA_E_CAPACITY or an allocation failure the resident rows and the counts are
+ * untouched. An add with n_seq == 0 or without a counted window succeeds, changes no row and
+ * counts in n_adds. The builder owns its two row buffers (grown geometrically) and its batch
+ * scratch (about 33 bytes per residue of the largest add, kept); an add whose buffers already fit
+ * allocates nothing.
+ * kma_sig_builder_finish does not change the builder: it may be called repeatedly and between
+ * adds; KMA_E_CAPACITY with *n_out = needed if cap is too small or an output is null with rows
+ * to write (n_out = info's n_role). KMA_E_INVALID before any device is touched: a null builder,
+ * out or n_out, k out of range, unknown flag bits. A builder is used by one thread at a time.
+ * kma_sig_builder_destroy frees it; NULL is allowed.                                          */
+typedef struct kma_sig_builder kma_sig_builder;
+struct kma_sig_builder_info {
+  int32_t k;
+  uint32_t flags;
+  uint32_t tile;          /* positions of the merged order one block of the merge takes */
+  uint32_t n_adds;
+  uint64_t n_residues;    /* summed over the adds that succeeded */
+  uint64_t n_keys, n_role, n_conflict, n_buffered;   /* resident rows, by state */
+  uint64_t bytes;         /* device memory held */
+};
+int kma_sig_builder_create(int k, uint32_t flags, int device, kma_sig_builder** out);
+int kma_sig_builder_add(kma_sig_builder* builder, const uint8_t* residues,
+                        const uint64_t* offsets, const int32_t* roles, uint32_t n_seq);
+int kma_sig_builder_info_get(const kma_sig_builder* builder, struct kma_sig_builder_info* out);
+int kma_sig_builder_finish(const kma_sig_builder* builder, uint64_t* out_keys,
+                           uint32_t* out_roles, uint64_t cap, uint64_t* n_out);
+int kma_sig_builder_destroy(kma_sig_builder* builder);
+
 /* ---- ProteinKmers.distance (genome/compare/GeneCopyProcessor.java:129-162) -----------------
  * One batch of proteins (residues, offsets, n_seq); pair i compares proteins pair_a[i] and
  * pair_b[i]. Sets are ProteinKmers of kmer size k (2..12, GeneCopyProcessor -K): the distinct

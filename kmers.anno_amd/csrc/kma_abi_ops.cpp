@@ -4,12 +4,15 @@
 // arguments on the host, enters its device, stages its batch in buffers of its own (kma_host.h:
 // upload_batch, Scratch, AlphabetFlag), runs its launchers (kma_build.hip, kma_proposals.hip,
 // kma_orf.hip, kma_translate.hip, kma_md5.hip) on the null stream and copies the results back.
+// The streamed signature build (kma_sig_builder, kma_sigmerge.hip) is here too: an object that
+// keeps its run and its scratch between calls.
 #include <memory>
 
 #include "kma_internal.h"
 #include "kma_md5.h"
 #include "kma_objects.h"
 #include "kma_orf.h"
+#include "kma_sigmerge.h"
 #include "kma_translate.h"
 
 using namespace kma::host;
@@ -146,6 +149,233 @@ int kma_build_signatures(const uint8_t* residues, const uint64_t* offsets, const
   if (n_sel == 0) return KMA_OK;
   KMA_HIP(hipMemcpy(out_keys, d_ka, n_sel * 8, hipMemcpyDeviceToHost));
   KMA_HIP(hipMemcpy(out_roles, d_ta, n_sel * 4, hipMemcpyDeviceToHost));
+  return KMA_OK;
+}
+
+}  // extern "C"
+
+// ---- streamed signature build (kma_sigmerge.hip) ------------------------------------------------
+// The builder's small device block: the LUT, then the words a call reads back.
+namespace {
+constexpr size_t kSigAlpha = 256, kSigNB = 264, kSigCounts = 272, kSigSmall = 304;
+
+uint64_t sig_builder_bytes(const kma_sig_builder* b) {
+  uint64_t n = kSigSmall;
+  for (int i = 0; i < 2; ++i) n += b->run_keys[i].cap * 8 + b->run_states[i].cap * 4;
+  n += b->in.cap + b->off.cap * 8 + b->roles.cap * 4 + (b->ka.cap + b->kb.cap) * 8;
+  n += (b->ta.cap + b->tb.cap + b->head.cap + b->run.cap) * 4 + b->hflags.cap;
+  return n + b->tiles.cap * 8 + b->temp.cap;
+}
+}  // namespace
+
+extern "C" {
+
+int kma_sig_builder_create(int k, uint32_t flags, int device, kma_sig_builder** out) {
+  if (!out) return fail(KMA_E_INVALID, "null argument");
+  *out = nullptr;
+  if (int rc = check_k(k)) return rc;
+  if (flags & ~KMA_F_END_EXCLUSIVE) return fail(KMA_E_INVALID, "bad flags");
+  uint8_t lut[256];
+  standard_lut(lut);
+  DeviceScope ds(device);
+  if (int rc = ds.entered()) return rc;
+  std::unique_ptr<kma_sig_builder> b(new kma_sig_builder);
+  b->device = device;
+  b->k = k;
+  b->flags = flags;
+  KMA_HIP(hipMalloc(reinterpret_cast<void**>(&b->d_small), kSigSmall));
+  KMA_HIP(hipMemset(b->d_small, 0, kSigSmall));
+  KMA_HIP(hipMemcpy(b->d_small, lut, 256, hipMemcpyHostToDevice));
+  for (hipEvent_t& e : b->ev) KMA_HIP(hipEventCreate(&e));
+  *out = b.release();
+  return KMA_OK;
+}
+
+int kma_sig_builder_destroy(kma_sig_builder* b) {
+  if (!b) return KMA_OK;
+  DeviceScope ds(b->device);
+  delete b;
+  return KMA_OK;
+}
+
+int kma_sig_builder_info_get(const kma_sig_builder* b, struct kma_sig_builder_info* out) {
+  if (!b || !out) return fail(KMA_E_INVALID, "null argument");
+  out->k = b->k;
+  out->flags = b->flags;
+  out->tile = kma::kSigTile;
+  out->n_adds = b->n_adds;
+  out->n_residues = b->n_residues;
+  out->n_keys = b->n_keys;
+  out->n_role = b->counts[0];
+  out->n_conflict = b->counts[1];
+  out->n_buffered = b->counts[2];
+  out->bytes = sig_builder_bytes(b);
+  return KMA_OK;
+}
+
+int kma_sig_builder_add(kma_sig_builder* b, const uint8_t* residues, const uint64_t* offsets,
+                        const int32_t* roles, uint32_t n_seq) {
+  if (!b) return fail(KMA_E_INVALID, "null argument");
+  if (n_seq == 0) return ++b->n_adds, KMA_OK;
+  if (!residues || !offsets || !roles) return fail(KMA_E_INVALID, "null argument");
+  for (uint32_t s = 0; s < n_seq; ++s) {
+    if (offsets[s + 1] < offsets[s]) return fail(KMA_E_INVALID, "offsets decrease at %u", s);
+    if (roles[s] >= (int32_t)kma::kBuildNeg)
+      return fail(KMA_E_INVALID, "role %d of protein %u >= 2^24 - 1", roles[s], s);
+  }
+  const uint64_t total = offsets[n_seq] - offsets[0];
+  if (total == 0) return ++b->n_adds, KMA_OK;
+  if (total >= (1ull << 31)) return fail(KMA_E_INVALID, "more than 2^31 residues in one add");
+  DeviceScope ds(b->device);
+  if (int rc = ds.entered()) return rc;
+  // the batch scratch (nothing of the resident run is touched before the swap at the end)
+  constexpr uint64_t kPad = 64;
+  KMA_HIP(b->in.reserve(total + kPad));
+  KMA_HIP(b->off.reserve(n_seq + 1ull));
+  KMA_HIP(b->roles.reserve(n_seq));
+  KMA_HIP(b->ka.reserve(total));
+  KMA_HIP(b->kb.reserve(total));
+  KMA_HIP(b->ta.reserve(total));
+  KMA_HIP(b->tb.reserve(total));
+  KMA_HIP(b->head.reserve(total));
+  KMA_HIP(b->run.reserve(total));
+  KMA_HIP(b->hflags.reserve(total));
+  uint64_t* const d_nb = reinterpret_cast<uint64_t*>(b->d_small + kSigNB);
+  uint32_t* const d_alpha = reinterpret_cast<uint32_t*>(b->d_small + kSigAlpha);
+  unsigned long long* const d_counts =
+      reinterpret_cast<unsigned long long*>(b->d_small + kSigCounts);
+  const int bits = 5 * b->k;
+  size_t need = 0, q = 0;
+  KMA_HIP(kma::launch_sort_pairs(nullptr, &q, b->ka.p, b->kb.p, b->ta.p, b->tb.p, total, bits,
+                                 nullptr));
+  need = std::max(need, q);
+  KMA_HIP(kma::launch_sig_reduce(b->kb.p, b->tb.p, total, b->hflags.p, b->head.p, b->run.p,
+                                 b->ka.p, b->ta.p, d_nb, nullptr, &q, nullptr));
+  need = std::max(need, q);
+  KMA_HIP(b->temp.reserve(need));
+  // stage, windows, sort, reduce
+  {
+    std::vector<uint64_t> rel(n_seq + 1ull);
+    rebase_offsets(rel.data(), offsets, n_seq + 1ull, offsets[0]);
+    KMA_HIP(hipMemcpy(b->in.p, residues + offsets[0], total, hipMemcpyHostToDevice));
+    KMA_HIP(hipMemset(b->in.p + total, 0, kPad));
+    KMA_HIP(hipMemcpy(b->off.p, rel.data(), (n_seq + 1ull) * 8, hipMemcpyHostToDevice));
+    KMA_HIP(hipMemcpy(b->roles.p, roles, n_seq * 4ull, hipMemcpyHostToDevice));
+  }
+  KMA_HIP(hipMemset(d_alpha, 0, 4));
+  KMA_HIP(hipMemset(d_nb, 0, 8));
+  KMA_HIP(hipEventRecord(b->ev[0], nullptr));
+  KMA_HIP(kma::launch_build_windows(b->in.p, b->off.p, n_seq, b->roles.p, b->k,
+                                    (b->flags & KMA_F_END_EXCLUSIVE) ? 1 : 0, b->d_small, b->ka.p,
+                                    b->ta.p, d_alpha, nullptr));
+  KMA_HIP(hipEventRecord(b->ev[1], nullptr));
+  q = b->temp.cap;
+  KMA_HIP(kma::launch_sort_pairs(b->temp.p, &q, b->ka.p, b->kb.p, b->ta.p, b->tb.p, total, bits,
+                                 nullptr));
+  KMA_HIP(hipEventRecord(b->ev[2], nullptr));
+  q = b->temp.cap;
+  KMA_HIP(kma::launch_sig_reduce(b->kb.p, b->tb.p, total, b->hflags.p, b->head.p, b->run.p,
+                                 b->ka.p, b->ta.p, d_nb, b->temp.p, &q, nullptr));
+  KMA_HIP(hipEventRecord(b->ev[3], nullptr));
+  uint64_t n_b = 0;
+  uint32_t alpha = 0;
+  KMA_HIP(hipMemcpy(&n_b, d_nb, 8, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(&alpha, d_alpha, 4, hipMemcpyDeviceToHost));
+  if (alpha) return fail(KMA_E_ALPHABET, "a protein window holds a byte outside A-Z and '*'");
+  if (n_b == 0) {  // no counted window
+    ++b->n_adds;
+    b->n_residues += total;
+    return KMA_OK;
+  }
+  // union merge of the resident run with the reduced batch into the other run buffer
+  const kma::SigRun ra{b->run_keys[b->cur].p, b->run_states[b->cur].p, b->n_keys};
+  const kma::SigRun rb{b->ka.p, b->ta.p, n_b};
+  const uint64_t n_tiles = kma::sig_tiles(ra.n, rb.n, kma::kSigTile);
+  KMA_HIP(b->tiles.reserve(2 * (n_tiles + 1)));
+  uint64_t* const tile_cnt = b->tiles.p;
+  uint64_t* const tile_off = b->tiles.p + n_tiles + 1;
+  KMA_HIP(kma::launch_sig_merge_count(ra, rb, tile_cnt, tile_off, nullptr, &q, nullptr));
+  KMA_HIP(b->temp.reserve(q));
+  q = b->temp.cap;
+  KMA_HIP(hipEventRecord(b->ev[4], nullptr));
+  KMA_HIP(kma::launch_sig_merge_count(ra, rb, tile_cnt, tile_off, b->temp.p, &q, nullptr));
+  KMA_HIP(hipEventRecord(b->ev[5], nullptr));
+  uint64_t n_out = 0;
+  KMA_HIP(hipMemcpy(&n_out, tile_off + n_tiles, 8, hipMemcpyDeviceToHost));
+  if (n_out >= (1ull << 32))
+    return fail(KMA_E_CAPACITY, "%llu resident keys: a builder holds fewer than 2^32",
+                (unsigned long long)n_out);
+  const int nxt = b->cur ^ 1;
+  KMA_HIP(b->run_keys[nxt].reserve(n_out));
+  KMA_HIP(b->run_states[nxt].reserve(n_out));
+  KMA_HIP(hipMemset(d_counts, 0, 24));
+  KMA_HIP(hipEventRecord(b->ev[6], nullptr));
+  KMA_HIP(kma::launch_sig_merge_write(ra, rb, tile_off, b->run_keys[nxt].p, b->run_states[nxt].p,
+                                      nullptr));
+  KMA_HIP(hipEventRecord(b->ev[7], nullptr));
+  KMA_HIP(kma::launch_sig_counts(b->run_states[nxt].p, n_out, d_counts, nullptr));
+  KMA_HIP(hipEventRecord(b->ev[8], nullptr));
+  uint64_t counts[3];
+  KMA_HIP(hipMemcpy(counts, d_counts, 24, hipMemcpyDeviceToHost));
+  const int first_event[6] = {0, 1, 2, 4, 6, 7};  // a stage runs from its event to the next one
+  for (int i = 0; i < 6; ++i) {
+    float ms = 0.f;
+    KMA_HIP(hipEventElapsedTime(&ms, b->ev[first_event[i]], b->ev[first_event[i] + 1]));
+    b->stage_ms[i] = ms;
+  }
+  b->cur = nxt;
+  b->n_keys = n_out;
+  std::copy(counts, counts + 3, b->counts);
+  ++b->n_adds;
+  b->n_residues += total;
+  return KMA_OK;
+}
+
+// Not in kmeranno.h: measurement hook (scripts/sigbuild_rate.py). hipEvent times of the stages of
+// the builder's last add that merged: windows, sort, reduce, the merge's count pass with its
+// scan, its write pass, the counts.
+int kma_debug_sig_builder_ms(const kma_sig_builder* b, double* out6) {
+  if (!b || !out6) return fail(KMA_E_INVALID, "null argument");
+  std::copy(b->stage_ms, b->stage_ms + 6, out6);
+  return KMA_OK;
+}
+
+int kma_sig_builder_finish(const kma_sig_builder* b, uint64_t* out_keys, uint32_t* out_roles,
+                           uint64_t cap, uint64_t* n_out) {
+  if (!b || !n_out) return fail(KMA_E_INVALID, "null argument");
+  const uint64_t n_sel = b->counts[0];
+  *n_out = n_sel;
+  if (n_sel > cap || (n_sel && (!out_keys || !out_roles)))
+    return fail(KMA_E_CAPACITY, "%llu signature kmers, capacity %llu",
+                (unsigned long long)n_sel, (unsigned long long)cap);
+  if (n_sel == 0) return KMA_OK;
+  DeviceScope ds(b->device);
+  if (int rc = ds.entered()) return rc;
+  // buffers of the call's own: the builder is left as it is
+  DevBufs bufs;
+  uint8_t* d_flags;
+  uint64_t *d_keys, *d_n;
+  uint32_t* d_roles;
+  KMA_HIP(bufs.alloc(&d_flags, b->n_keys));
+  KMA_HIP(bufs.alloc(&d_keys, n_sel * 8));
+  KMA_HIP(bufs.alloc(&d_roles, n_sel * 4));
+  KMA_HIP(bufs.alloc(&d_n, 8));
+  const uint64_t* keys = b->run_keys[b->cur].p;
+  const uint32_t* states = b->run_states[b->cur].p;
+  Scratch tmp;
+  KMA_HIP(kma::launch_select_flagged(nullptr, tmp.ask(), keys, states, d_flags, d_keys, d_roles,
+                                     d_n, b->n_keys, nullptr));
+  KMA_HIP(tmp.alloc(bufs));
+  KMA_HIP(kma::launch_sig_role_flags(states, b->n_keys, d_flags, nullptr));
+  KMA_HIP(kma::launch_select_flagged(tmp.p, tmp.bytes(), keys, states, d_flags, d_keys, d_roles,
+                                     d_n, b->n_keys, nullptr));
+  uint64_t got = 0;
+  KMA_HIP(hipMemcpy(&got, d_n, 8, hipMemcpyDeviceToHost));
+  if (got != n_sel)
+    return fail(KMA_E_DEVICE, "%llu rows selected, %llu counted", (unsigned long long)got,
+                (unsigned long long)n_sel);
+  KMA_HIP(hipMemcpy(out_keys, d_keys, n_sel * 8, hipMemcpyDeviceToHost));
+  KMA_HIP(hipMemcpy(out_roles, d_roles, n_sel * 4, hipMemcpyDeviceToHost));
   return KMA_OK;
 }
 

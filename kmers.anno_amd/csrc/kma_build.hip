@@ -579,6 +579,20 @@ hipError_t launch_build_windows(const uint8_t* residues, const uint64_t* offsets
   return hipGetLastError();
 }
 
+hipError_t launch_signature_heads(const uint64_t* keys, uint64_t n, uint8_t* flags,
+                                  uint32_t* head_idx, uint32_t* run, void* temp,
+                                  size_t* temp_bytes, hipStream_t stream) {
+  if (!temp)
+    return rocprim::inclusive_scan(nullptr, *temp_bytes, head_idx, run, (size_t)n,
+                                   rocprim::maximum<uint32_t>(), stream);
+  hipLaunchKernelGGL(sig_heads_kernel, dim3(grid_for(n)), dim3(256), 0, stream, keys, n, flags,
+                     head_idx);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return rocprim::inclusive_scan(temp, *temp_bytes, head_idx, run, (size_t)n,
+                                 rocprim::maximum<uint32_t>(), stream);
+}
+
 hipError_t launch_signature_flags(const uint64_t* keys, const uint32_t* tags, uint64_t n,
                                   uint8_t* flags, uint32_t* head_idx, uint32_t* run, void* temp,
                                   size_t* temp_bytes, hipStream_t stream) {

@@ -572,6 +572,12 @@ hipError_t launch_build_windows(const uint8_t* residues, const uint64_t* offsets
 hipError_t launch_signature_flags(const uint64_t* keys, const uint32_t* tags, uint64_t n,
                                   uint8_t* flags, uint32_t* head_idx, uint32_t* run, void* temp,
                                   size_t* temp_bytes, hipStream_t stream);
+// The first two steps of launch_signature_flags alone, for the streamed build (kma_sigmerge.hip):
+// flags[i] = 1 for the first pair of every run of equal non-zero keys, run[i] = the index of the
+// head at or before i (temp == nullptr: size query).
+hipError_t launch_signature_heads(const uint64_t* keys, uint64_t n, uint8_t* flags,
+                                  uint32_t* head_idx, uint32_t* run, void* temp,
+                                  size_t* temp_bytes, hipStream_t stream);
 hipError_t launch_select_flagged(void* temp, size_t* temp_bytes, const uint64_t* keys_in,
                                  const uint32_t* vals_in, const uint8_t* flags, uint64_t* keys_out,
                                  uint32_t* vals_out, uint64_t* n_out, uint64_t n,

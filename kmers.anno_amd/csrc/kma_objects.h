@@ -107,6 +107,51 @@ struct kma_proto_index {
   }
 };
 
+// The streamed signature build (kma_sigmerge.h): the resident run of unique ascending keys with
+// their states in run_*[cur], the merge target in run_*[cur ^ 1] (swapped in when an add has
+// succeeded), and the batch scratch, kept at the largest size seen. Used by one thread at a time.
+struct kma_sig_builder {
+  int device = 0;
+  int k = 8;
+  uint32_t flags = 0;
+  uint32_t n_adds = 0;
+  uint64_t n_residues = 0;
+  uint64_t n_keys = 0;        // rows of the resident run
+  uint64_t counts[3] = {};    // of them: role / conflict / buffered
+  int cur = 0;
+  kma::host::Grow<uint64_t> run_keys[2];
+  kma::host::Grow<uint32_t> run_states[2];
+  // batch scratch: the staged batch, the (key, tag) pairs before and after the sort (the reduced
+  // batch lands in ka / ta), head indices then states, run ids, head flags, the merge's tile
+  // counts and offsets, the sort / scan / select scratch
+  kma::host::Grow<uint8_t> in;
+  kma::host::Grow<uint64_t> off;
+  kma::host::Grow<int32_t> roles;
+  kma::host::Grow<uint64_t> ka, kb;
+  kma::host::Grow<uint32_t> ta, tb, head, run;
+  kma::host::Grow<uint8_t> hflags;
+  kma::host::Grow<uint64_t> tiles;
+  kma::host::Grow<uint8_t> temp;
+  uint8_t* d_small = nullptr;  // the LUT (256 B), then alpha flag, reduced count, state counts
+  // the last merging add's stages (kma_debug_sig_builder_ms): events around windows, sort,
+  // reduce, the merge's count pass with its scan, its write pass, the counts
+  hipEvent_t ev[9] = {};
+  double stage_ms[6] = {};
+  kma_sig_builder() = default;
+  kma_sig_builder(const kma_sig_builder&) = delete;
+  kma_sig_builder& operator=(const kma_sig_builder&) = delete;
+  ~kma_sig_builder() {
+    for (auto& g : run_keys) g.release();
+    for (auto& g : run_states) g.release();
+    in.release(), off.release(), roles.release(), ka.release(), kb.release(), ta.release();
+    tb.release(), head.release(), run.release(), hflags.release(), tiles.release();
+    temp.release();
+    if (d_small) (void)hipFree(d_small);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 namespace kma {
 namespace host {
 // ---- tables (kma_abi_table.cpp) -----------------------------------------------------------------

@@ -51,6 +51,8 @@ EXPORTS = (
     "kma_proto_index_create", "kma_proto_index_info", "kma_proto_index_destroy",
     "kma_hash_annotate_indexed",
     "kma_hash_scratch_bytes", "kma_hash_annotate_indexed_device",
+    "kma_sig_builder_create", "kma_sig_builder_add", "kma_sig_builder_info_get",
+    "kma_sig_builder_finish", "kma_sig_builder_destroy",
 )
 
 # Tuning options (include/kmeranno.h "options"): library-wide defaults read per call.
@@ -93,6 +95,13 @@ class TableInfo(C.Structure):
 class ProtoIndexInfo(C.Structure):
     _fields_ = [("n_proto", C.c_uint32), ("k", C.c_int32), ("n_keys", C.c_uint64),
                 ("n_postings", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class SigBuilderInfo(C.Structure):
+    _fields_ = [("k", C.c_int32), ("flags", C.c_uint32), ("tile", C.c_uint32),
+                ("n_adds", C.c_uint32), ("n_residues", C.c_uint64), ("n_keys", C.c_uint64),
+                ("n_role", C.c_uint64), ("n_conflict", C.c_uint64), ("n_buffered", C.c_uint64),
+                ("bytes", C.c_uint64)]
 
 
 HIT_DTYPE = np.dtype([("contig", "<u4"), ("left", "<i4"), ("fid", "<u4"), ("strand", "u1"),
@@ -171,6 +180,11 @@ def load(path: str | None = None):
                                                   _u64, _vp, _vp, _u32, _vp]
         L.kma_build_signatures.argtypes = [_u8p, _u64p, _i32p, _u32, _int, _u32, _int, _vp, _vp,
                                            _u64, C.POINTER(_u64)]
+        L.kma_sig_builder_create.argtypes = [_int, _u32, _int, C.POINTER(_vp)]
+        L.kma_sig_builder_add.argtypes = [_vp, _vp, _vp, _vp, _u32]
+        L.kma_sig_builder_info_get.argtypes = [_vp, C.POINTER(SigBuilderInfo)]
+        L.kma_sig_builder_finish.argtypes = [_vp, _vp, _vp, _u64, C.POINTER(_u64)]
+        L.kma_sig_builder_destroy.argtypes = [_vp]
         L.kma_peg_table_create.argtypes = [_u8p, _u64p, _u32, _int, _int, C.c_double,
                                            C.POINTER(_vp), C.POINTER(_u64)]
         L.kma_connect_pegs.argtypes = [_vp, _u8p, _u64p, _u32, _int, _int, _vp, _u64,
@@ -973,6 +987,71 @@ def build_signatures(residues: np.ndarray, offsets: np.ndarray, roles, k: int = 
             continue
         _check(rc)
         return keys[:nout.value], rl[:nout.value]
+
+
+class SigBuilder:
+    """kma_sig_builder: build_signatures for a training set fed batch by batch. Every add folds
+    its proteins into the rows resident on the GPU (one per distinct kmer, with its state);
+    finish() returns what build_signatures returns for the concatenation of the adds, whatever
+    the split into adds and their order. A context manager; one thread at a time."""
+
+    def __init__(self, k: int = 8, flags: int = 0, device: int = 0):
+        self._h = _vp()
+        _check(load().kma_sig_builder_create(k, flags, device, C.byref(self._h)))
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise KmerAnnoError(E_INVALID, "the signature builder is closed")
+        return self._h
+
+    def add(self, residues, offsets, roles):
+        """One batch: roles[s] >= 0 the single good role of an interesting peg, -1 a buffered
+        protein, any other negative value a skipped one. All-or-nothing."""
+        residues = np.ascontiguousarray(residues, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        roles = np.ascontiguousarray(roles, np.int32)
+        n = len(offsets) - 1
+        if len(roles) != n:
+            raise KmerAnnoError(E_INVALID, f"{len(roles)} roles for {n} proteins")
+        if not len(residues):
+            residues = np.zeros(1, np.uint8)
+        if not len(roles):
+            roles = np.zeros(1, np.int32)
+        _check(load().kma_sig_builder_add(self.handle, residues.ctypes.data, offsets.ctypes.data,
+                                          roles.ctypes.data, n))
+
+    def info(self) -> SigBuilderInfo:
+        out = SigBuilderInfo()
+        _check(load().kma_sig_builder_info_get(self.handle, C.byref(out)))
+        return out
+
+    def finish(self):
+        """(packed keys, roles) of the discriminating kmers so far, key order; the builder is
+        left as it is."""
+        n = int(self.info().n_role)
+        keys, rl, nout = np.empty(n, np.uint64), np.empty(n, np.uint32), _u64()
+        _check(load().kma_sig_builder_finish(self.handle, keys.ctypes.data, rl.ctypes.data, n,
+                                             C.byref(nout)))
+        assert nout.value == n
+        return keys, rl
+
+    def close(self):
+        if self._h:
+            load().kma_sig_builder_destroy(self._h)
+            self._h = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def contig_window_count(offsets: np.ndarray, k: int = 8) -> int:
